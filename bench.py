@@ -4,6 +4,7 @@
   python bench.py --gpus 1 --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+  python bench.py ... --dump-outputs DIR      (also writes what the last timed step computed: DIR/<name>.npy, see dump_outputs)
 
 One step = zero_grad + Flowtron.forward + FlowtronLoss (NLL + gate + attention-CTC) + backward (with ONE in-place RCCL
 all-reduce(AVG) of the flat gradient arena at the end of backward when N > 1; per-flow buckets under backward with FLOWTRON_DP_OVERLAP=1) + global-norm clip + fused RAdam update, on BASELINE.json configs[1]:
@@ -737,6 +738,49 @@ def trainpy_step_block(model, criterion, optimizer, batch_cpu, steps, warmup, us
             "final_loss": round(reduced[0], 5), "T_max": int(mel.shape[2]), "L_max": int(txt.shape[1])}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_ELEMS = 1 << 20           # per array: a larger one is written as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(out_dir, last, model):
+    """--dump-outputs: what the timed path computed in its last step (which main() starts from the run's initial, seeded state,
+    so that it is the same in every run), as <out_dir>/<name>.npy -- the loss terms (float64), every
+    tensor of Flowtron.forward's 8-tuple, and the gradients and updated parameters (flattened in named_parameters() order).  An
+    array above DUMP_MAX_ELEMS elements (fewer when there are many arrays: 64 MB in all) is written flattened, as a sample at
+    fixed seeded indices (sorted, the same in every run of the same shape)."""
+    arrays = {}
+    for k in ("loss", "nll", "gate_loss", "ctc_loss"):
+        if k in last:
+            arrays[k] = last[k].detach().reshape(-1).double()
+
+    def walk(name, x):
+        if torch.is_tensor(x):
+            arrays[name] = x.detach()
+        elif isinstance(x, (list, tuple)):
+            for i, y in enumerate(x):
+                walk("%s_%d" % (name, i), y)
+    for i, (nm, x) in enumerate(zip(("z", "log_s", "gate", "attn", "attn_logprob", "mean", "log_var", "prob"), last.get("out", ()))):
+        walk("out%d_%s" % (i, nm), x)
+    params = [p for p in model.parameters()]
+    with torch.no_grad():
+        arrays["params"] = torch.cat([p.detach().reshape(-1).float() for p in params])
+        arrays["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                     for p in params])
+    os.makedirs(out_dir, exist_ok=True)
+    cap = min(DUMP_MAX_ELEMS, DUMP_BUDGET_BYTES // (8 * len(arrays)))
+    total = 0
+    for name, t in arrays.items():
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_BUDGET_BYTES, total
+    return sorted(arrays)
+
+
 def main():
     if len(sys.argv) >= 4 and sys.argv[1] == "--cpu-baseline-worker":
         print(json.dumps(cpu_baseline_worker(int(sys.argv[2]), int(sys.argv[3]), sys.argv[4] if len(sys.argv) > 4 else None)), flush=True)
@@ -759,6 +803,8 @@ def main():
     ap.add_argument("--no-pad-hidden", action="store_true",
                     help="with --hidden < 1024: the launch-per-step recurrence kernels instead of the zero-padded persistent ones (yardstick)")
     ap.add_argument("--no-trainpy", action="store_true", help="skip the train.py-call-sequence block (trainpy_step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -824,11 +870,15 @@ def main():
     # fp16 operands: the reference's AMP step (train.py:292-331) -- GradScaler around backward, unscale_, clip, scaler.step
     scaler = torch.amp.GradScaler("cuda", enabled=args.mfma == "f16")
 
+    last = {}                                                  # --dump-outputs: the last step's results
+
     def step():
         optimizer.zero_grad()
         out = model(b["mel"], b["speaker_ids"], b["text"], b["in_lens"], b["out_lens"], prior)
         nll, gl, ctc = criterion(out, b["gate"], b["in_lens"], b["out_lens"])
         loss = nll + gl + criterion.ctc_loss_weight * ctc
+        if args.dump_outputs:
+            last.update(out=out, loss=loss, nll=nll, gate_loss=gl, ctc_loss=ctc)
         if scaler.is_enabled():
             scaler.scale(loss).backward()
             scaler.unscale_(optimizer)
@@ -863,6 +913,23 @@ def main():
         model.train()
         optimizer.zero_grad()
 
+    snapshot = None
+    if args.dump_outputs:
+        # the backward reduces with fp32 atomics, so the state that W + K - 1 updates reach differs from run to run in its last bits
+        # and the 16-bit weight images carry that into the forward: the last timed step starts from this (seeded, fixed) state
+        # instead, so that what it computes -- and --dump-outputs writes -- is the same in every run up to rounding
+        import copy
+        snapshot = {"params": [p.detach().clone() for p in model.parameters()], "opt": copy.deepcopy(optimizer.state_dict()),
+                    "scaler": copy.deepcopy(scaler.state_dict()), "rng": torch.cuda.get_rng_state()}
+
+    def restore():
+        with torch.no_grad():
+            for p, q in zip(model.parameters(), snapshot["params"]):
+                p.copy_(q)
+        optimizer.load_state_dict(copy.deepcopy(snapshot["opt"]))
+        scaler.load_state_dict(snapshot["scaler"])
+        torch.cuda.set_rng_state(snapshot["rng"])
+
     log("model + batch ready (%d valid frames/step); warm-up" % frames_rank)
     for _ in range(args.warmup):
         loss = step()
@@ -882,7 +949,13 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if snapshot is not None and i == args.steps - 1:      # (untimed: the clock stops while the state is put back)
+            torch.cuda.synchronize()
+            t_pause = time.perf_counter()
+            restore()
+            torch.cuda.synchronize()
+            t0 += time.perf_counter() - t_pause
         loss = step()
     torch.cuda.synchronize()
     if world > 1:
@@ -896,8 +969,14 @@ def main():
         comm_ms = sum(a.elapsed_time(b) for a, b in evs) / len(evs)
         model._comm_timing = False
     from flowtron_amd import ops as _ops_chk
-    _ops_chk.check_persist_status()                              # a persistent recurrence that timed out would have produced garbage
+    # a persistent recurrence that timed out would have produced garbage -- except under the BENCH_SHARED_GPU test hook, where the
+    # ranks' whole-chip grids share one device and may meet: the device-side guard drops that step on every rank (skipped_steps)
+    persist_ok = _ops_chk.check_persist_status(raise_on_failure=not shared_gpu)
+    persist_failures = sum(int(st.failures) for st in _ops_chk._PERSIST.values())
     loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        log("outputs of the last timed step -> %s: %s" % (args.dump_outputs, ", ".join(dump_outputs(args.dump_outputs, last, model))))
+        last.clear()
     stats = torch.tensor([dt, float(frames_rank)], dtype=torch.float64, device="cuda")
     comm_all = None
     if world > 1:
@@ -936,6 +1015,12 @@ def main():
                        **({"test_hook": "BENCH_SHARED_GPU: all ranks on ONE GPU over gloo -- not a scaling measurement"} if shared_gpu else {})},
         }
         res["config"]["skipped_steps"] = skipped             # updates dropped by the device-side non-finite-norm guard (0 = none)
+        if shared_gpu:                                       # persistent launches of this rank that timed out (their steps were dropped)
+            res["config"]["persist_failures"] = persist_failures
+            res["config"]["persist_ok_at_end"] = bool(persist_ok)
+        if snapshot is not None:
+            res["config"]["dump_outputs"] = ("the last timed step started from the run's initial state (weights, RAdam state, GradScaler, "
+                                             "RNG): final_loss is that step's loss, not the loss after the earlier updates")
         n1_path = os.path.join(os.environ.get("TMPDIR", "/tmp"), "flowtron_bench_n1_%s.json" % args.config)
         if world == 1:
             try:

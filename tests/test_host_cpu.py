@@ -47,12 +47,10 @@ def test_state_dict_layout_matches_reference_spec():
 
 
 def test_reference_config_json_schema_is_accepted():
-    """config.json's model_config keys are splatted into the ctor (train.py:221): the key set IS the signature."""
-    ref_cfg = os.path.join("/root/reference", "config.json")
-    if not os.path.exists(ref_cfg):
-        pytest.skip("reference not mounted")
+    """config.json's model_config keys are splatted into the ctor (train.py:221): the key set IS the signature.
+    (tests/golden/ref_api.json holds the reference's config.json values: tests/golden/make_golden_ref_api.py)"""
     import flowtron
-    cfg = json.load(open(ref_cfg))
+    cfg = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_api.json")))["config"]
     m = flowtron.Flowtron(**cfg["model_config"])
     assert len(m.flows) == cfg["model_config"]["n_flows"]
     t = cfg["train_config"]
@@ -425,3 +423,30 @@ def test_product_path_never_touches_the_oracle():
             assert not any(n == "oracle" or n.startswith("oracle.") for n in names), (path, names)
     for f in os.listdir(os.path.join(pkg, "csrc")):
         assert "oracle" not in open(os.path.join(pkg, "csrc", f), errors="ignore").read().lower() or f.endswith(".md"), f
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """bench.py --dump-outputs: loss terms in float64, every forward tensor and the flat gradients / parameters in float32, large
+    arrays as a seeded sample that is the same in every run, 64 MB in all."""
+    import numpy as np
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Linear(3000, 1000)
+    m(torch.randn(2, 3000)).sum().backward()
+    last = dict(out=(torch.randn(80, 900, 32), [torch.randn(5, 5), torch.randn(5, 5)], torch.randn(32, 900), [], [], None, None, None),
+                loss=torch.tensor(1.5), nll=torch.tensor(1.0), gate_loss=torch.tensor(0.2), ctc_loss=torch.tensor(3.0))
+    names = bench.dump_outputs(str(tmp_path / "a"), last, m)
+    bench.dump_outputs(str(tmp_path / "b"), last, m)
+    assert names == sorted(["loss", "nll", "gate_loss", "ctc_loss", "out0_z", "out1_log_s_0", "out1_log_s_1", "out2_gate", "params",
+                            "grads"])
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == (np.float64 if n in ("loss", "nll", "gate_loss", "ctc_loss") else np.float32), n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= bench.DUMP_BUDGET_BYTES
+    assert np.load(tmp_path / "a" / "out1_log_s_0.npy").shape == (5, 5)
+    assert np.load(tmp_path / "a" / "loss.npy")[0] == 1.5
+    z = np.load(tmp_path / "a" / "out0_z.npy")
+    assert z.ndim == 1 and 0 < z.size <= bench.DUMP_MAX_ELEMS and np.isin(z, last["out"][0].numpy().reshape(-1)).all()

@@ -857,7 +857,9 @@ __global__ __launch_bounds__(256, 1) void lstm_roles_bwd_k(BwdLaunchP P) {
                     for (int g = 0; g < 4; ++g) dg[(size_t)g * PH] = 0.f;
                 }
             }
-            if (p.st_da && NS > 0) {
+            // (also a group without steps in a non-empty window: it has none in any later one either, so its state is zero -- written, so
+            // that an earlier window with carry_in reads zeros and not whatever the buffer held before the first window)
+            if (p.st_da && (NS > 0 || p.t1 > t0)) {
                 p.st_dc[eb * PH + eu] = dc_carry[e];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) p.st_da[(eb * 4 + g) * PH + eu] = da[e][g];
@@ -952,7 +954,9 @@ extern "C" int FT_OPNAME(ft_lstm_roles_fwd)(const ft_lstm_fwd_role* roles, int n
         g16 = r.gx16 != 0;
         any = any || r.t1 > r.t0;
     }
-    if (!any) return FT_OK;
+    // a launch with every window empty would do nothing, yet its caller counts it in `phase`: the next real launch would then work in
+    // the wrong hand-off set.  Refused, so that the caller skips the call and keeps its count.
+    if (!any) return ft_fail(FT_EINVAL, "ft_lstm_roles_fwd: every window is empty (t1 == t0): nothing to launch");
     char* base = reinterpret_cast<char*>(ctx);
     P.nroles = n_roles;
     P.census = reinterpret_cast<unsigned*>(base);
@@ -997,7 +1001,7 @@ extern "C" int FT_OPNAME(ft_lstm_roles_bwd)(const ft_lstm_bwd_role* roles, int n
                              r.B, r.ldb, r.t0, r.t1, r.carry_in};
         any = any || r.t1 > r.t0;
     }
-    if (!any) return FT_OK;
+    if (!any) return ft_fail(FT_EINVAL, "ft_lstm_roles_bwd: every window is empty (t1 == t0): nothing to launch");     // (as in the forward)
     char* base = reinterpret_cast<char*>(ctx);
     P.nroles = n_roles;
     P.census = reinterpret_cast<unsigned*>(base + 64);

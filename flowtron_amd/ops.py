@@ -582,7 +582,7 @@ class LinearFn(torch.autograd.Function):
         if split_fwd:
             assert len(xs) == 1 and act == L.ACT_NONE and L.is16(mode_dx) and mode_dx == mode_dw
             x2d = xs[0].reshape(rows, Ktot)
-            split_imgs = None
+            split_imgs = lazy = None
             if Ktot % 32 == 0 and images_apply(mode_dx, rows, N, Ktot):
                 lazy = _LAZY_COLS.pop(xs[0].data_ptr(), None)     # (an Im2colFn output whose values were never written: image from ITS source)
                 xi = Bf16Image.split3_im2col(*lazy, mode_dx) if lazy is not None else Bf16Image.split3(x2d, mode_dx, False)
@@ -604,6 +604,9 @@ class LinearFn(torch.autograd.Function):
             rowmap = None
         ctx.imgs = split_imgs if split_fwd else None
         ctx.cat = False
+        # how the images were made, to make them again for a second backward through the graph (retain_graph: the first one releases them)
+        ctx.img_kind = ("split3" if split_imgs is not None else None) if split_fwd else ("images" if use_img else None)
+        ctx.lazy_src = lazy if split_fwd else None
         if use_img:
             w_img = Bf16Image.of_weight(W, mode)
             if len(xs) > 1 and rowmap is not None and _CAT_IMAGES:
@@ -647,7 +650,9 @@ class LinearFn(torch.autograd.Function):
         N, Ktot = W.shape
         rows = dy.numel() // N
         rowmap = ctx.rowmap
-        if ctx.imgs is None and ctx.lazy_img_mode is not None:
+        if ctx.imgs is None and ctx.img_kind is not None:
+            ctx.imgs = _linear_images_again(ctx, W, xs, rows)
+        elif ctx.imgs is None and ctx.lazy_img_mode is not None:
             lm = ctx.lazy_img_mode
             ctx.imgs = (Bf16Image(W, mode=lm), [shared_image(x, rows, x.shape[-1], lm, rowmap) for x in xs])
         # an image handed over by the producer of dy (the LSTM backward) is looked up on dy AS IT ARRIVES: an image-only gradient is
@@ -724,6 +729,21 @@ class LinearFn(torch.autograd.Function):
         return (dW, db, None, None, None, None, *dxs)
 
 
+def _linear_images_again(ctx, W, xs, rows):
+    """the operand images a LinearFn forward made, made again from the same sources for a second backward through the graph: the
+    split [hi] blocks of the encoder convolution (from x itself where the column matrix was never written), the concatenated or
+    per-input compact images of the image path"""
+    Ktot = W.shape[1]
+    if ctx.img_kind == "split3":
+        m = ctx.mode_dx
+        xi = Bf16Image.split3_im2col(*ctx.lazy_src, m) if ctx.lazy_src is not None else Bf16Image.split3(xs[0].reshape(rows, Ktot), m, False)
+        return Bf16Image.of_weight(W, m, split=True).view_cols(Ktot), [xi.view_cols(Ktot)]
+    w_img = Bf16Image.of_weight(W, ctx.mode)
+    if ctx.cat:
+        return w_img, [Bf16Image.cat_rows([x.reshape(rows, x.shape[-1]) for x in xs], ctx.mode, ctx.rowmap)]
+    return w_img, [shared_image(x, rows, x.shape[-1], ctx.mode, ctx.rowmap) for x in xs]
+
+
 _GATE_ON_CAT = True        # the gate layer on the decoder input projection's concatenated image (round 4)
 
 
@@ -771,6 +791,8 @@ class LinearGateFn(torch.autograd.Function):
         N, Ktot = W.shape
         rowmap = ctx.rowmap
         rows = rowmap.T * rowmap.B
+        if ctx.imgs is None:                           # (released by a first backward through the graph: retain_graph)
+            ctx.imgs = (Bf16Image.of_weight(W, ctx.mode), Bf16Image.cat_rows([x.reshape(rows, x.shape[-1]) for x in xs], ctx.mode, rowmap))
         w_img, x_cat = ctx.imgs
         want_db = ctx.has_bias and ctx.needs_input_grad[1]
         d_img = _handoff_take(dy)                      # the LSTM backward's dgates image (possibly the ONLY form dy exists in)
@@ -1276,7 +1298,11 @@ def bwd_role(dy, lens, gates, cell, dgx, wimg, t0=0, t1=None, state=None, carry_
 
 
 def roles_launch(roles, R, mode, device, backward=False, H=1024):
-    """one launch of lstm_roles_fwd_k / _bwd_k: `roles` = one or two role structs; R rows per XCD group"""
+    """one launch of lstm_roles_fwd_k / _bwd_k: `roles` = one or two role structs; R rows per XCD group.  Nothing happens when every
+    window is empty: the C entries refuse such a call (FT_EINVAL), and a launch counted in `phase` that never ran would leave the next
+    one in the wrong hand-off set."""
+    if all(r.t1 <= r.t0 for r in roles):
+        return
     c = roles_ctx(device)
     if R > c.reset_rows:
         # wider groups than any launch on this context has preset for: start over with the sets preset for R rows (rare: the first
@@ -1399,7 +1425,7 @@ class DecoderPairFn(torch.autograd.Function):
         # layer 0's dgates leave as the compact 16-bit image alone where the only consumer is the input projection's backward
         img_ok = rm is not None and _PERSIST_IMG != "0" and images_apply(mode, H4, H, (T - 1) * B) and (ctx.gx_private or _PERSIST_IMG == "both")
         img_only = img_ok and _PERSIST_IMG != "both" and not torch.is_anomaly_enabled()
-        w_img = ctx.w_img
+        w_img = ctx.w_img if ctx.w_img is not None else Bf16Image.of_weight(w_ih1, mode)     # (released by a first backward: retain_graph)
         ctx.w_img = None
         nb = _PAIR_CHUNKS_BWD if _PAIR_CHUNKS_BWD >= 0 else n
         if nb == 0 and rm is not None and img_ok and ctx.needs_input_grad[1] and ctx.needs_input_grad[5]:
@@ -1479,9 +1505,9 @@ def _pair_backward_sequential(ctx, dy1, w_img, img_only):
     code = PERSIST_BWD_CODE
     work = torch.empty(L.lib().ft_lstm_persist_workspace_bytes(B, H), device=dev, dtype=torch.uint8)
 
-    def recurrence(dy, g, c, w_hh):
+    def recurrence(dy, g, c, w_hh, dgx=None):
         img = Bf16Image.empty_rows(H4, rm, mode, dev)
-        L.check(L.op16("ft_lstm_persist_bwd_img", mode)(L.ptr(dy), H, L.ptr(w_hh), L.ptr(lens), L.ptr(g), L.ptr(c), None, L.ptr(work), L.ptr(st.status),
+        L.check(L.op16("ft_lstm_persist_bwd_img", mode)(L.ptr(dy), H, L.ptr(w_hh), L.ptr(lens), L.ptr(g), L.ptr(c), L.ptr(dgx), L.ptr(work), L.ptr(st.status),
                                                         T, B, H, code, L.ptr(img.buf), img.ld, img.buf.numel() // (2 * img.ld), L.ptr(img.colsum), L.stream()),
                 "ft_lstm_persist_bwd_img")
         _persist_arm(st)
@@ -1494,10 +1520,18 @@ def _pair_backward_sequential(ctx, dy1, w_img, img_only):
     dy0 = torch.empty(T, B, H, device=dev, dtype=torch.float32)
     gemm_img(d_img1, 0, d_img1.ptr(), w_img, 1, w_img.ptr(), dy0, rm.cap, H, H4, H, rowmap=rm, compact=1)
     gemm_img(d_img1, 1, d_img1.ptr(), y0_img, 1, y0_img.ptr(), dW_ih1, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2)
-    d_img0 = recurrence(dy0, g0, c0, w_hh0)
+    # layer 0's dgates: the image alone, or (anomaly mode, FLOWTRON_LSTM_PERSIST_IMG=both) fp32 rows beside it -- real values for a
+    # consumer that reads them, as LSTMSeqFn.backward
+    dgx0 = None if img_only else torch.empty(T, B, H4, device=dev, dtype=torch.float32)
+    d_img0 = recurrence(dy0, g0, c0, w_hh0, dgx0)
     gemm_img(d_img0, 1, d_img0.ptr(1), y0_img, 1, y0_img.ptr(0), dW_hh0, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=1)
-    dgx0 = image_only_gradient((T, B, H4), dev, ctx.gx_dtype)
-    _handoff_put_image_only(dgx0, d_img0)
+    if img_only:
+        dgx0 = image_only_gradient((T, B, H4), dev, ctx.gx_dtype)
+        _handoff_put_image_only(dgx0, d_img0)
+    else:
+        if ctx.gx_dtype != torch.float32:
+            dgx0 = dgx0.to(ctx.gx_dtype)
+        _handoff_put(dgx0, d_img0)
     db1 = d_img1.colsum
     return dgx0, dW_hh0, dW_ih1, db1, db1, dW_hh1, None, None, None, None, None
 

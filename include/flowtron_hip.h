@@ -303,7 +303,9 @@ int ft_lstm_persist_bwd_img(const float* dy, int64_t ldy, const float* w_hh, con
  * (forward / backward) on this ctx -- a launch works in hand-off set phase & 1 and presets set (phase + 1) & 1 for `reset_rows` (>= the R
  * of the next launch of its kind) while it runs, so no preset dispatch precedes a launch.  Launches on one ctx must be serialised on
  * one stream.  `status` as for ft_lstm_persist_*.  Forward results are bit-identical to ft_lstm_seq_fwd for every R / windowing / role
- * placement; backward to fp32 rounding (R = 4: bit-identical to ft_lstm_persist_bwd's reduce-scatter transport). */
+ * placement; backward to fp32 rounding (R = 4: bit-identical to ft_lstm_persist_bwd's reduce-scatter transport).  A call in which EVERY
+ * role's window is empty (t1 == t0) is refused with FT_EINVAL and launches nothing: it must not be counted in `phase` (a launch counted
+ * that never ran would leave the next one in the wrong hand-off set).  One empty role beside a non-empty one is fine. */
 typedef struct {
     const void* gx; const int32_t* lens; float* y; int64_t ldy; float* gates; float* cell;   /* as ft_lstm_seq_fwd; time steps ldb rows apart */
     const void* wimg;
@@ -317,7 +319,8 @@ typedef struct {
     float* dgx;                          /* fp32 dgates rows [T][ldb][4H], or NULL when only the image is wanted */
     const void* wimg;
     void* dimg; int64_t dimg_ld; int64_t dimg_rows; float* dbias;    /* optional: as ft_lstm_persist_bwd_img (needs ldb == B) */
-    float* state_da; float* state_dc;    /* [B][4H], [B][H] fp32: read when carry_in, written at the end of the window */
+    float* state_da; float* state_dc;    /* [B][4H], [B][H] fp32: read when carry_in, written at the end of a non-empty window (zeros for rows
+                                          * whose group has no step in it): the buffers need no initialisation */
     int32_t B, ldb, t0, t1, carry_in;    /* carry_in: the window [t1, ..) has run before and left its state */
 } ft_lstm_bwd_role;
 size_t ft_lstm_roles_ctx_bytes(void);

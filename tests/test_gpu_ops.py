@@ -1483,3 +1483,193 @@ def test_fused_cumulative_attention_frames_vs_float64_reference(env, monkeypatch
         report.append(("d" + nm, ef, ec))
         assert ef <= 2.0 * ec + 5e-3 and ef < 6e-2, report
     print("\n[fused cumulative attention fmt %d T %d L %d] (name, fused vs f64, chain vs f64): %s" % (fmt, T, Lk, report))
+
+
+# ---------------------------------------------------------------- the decoder pair's backward: anomaly mode, `both`, a second backward
+def _pair_setup(T=48, B=32, K=128, seed=3):
+    import torch.nn as nn
+    torch.manual_seed(seed)
+    p = nn.LSTM(K, 1024, 2).cuda()
+    lens = torch.randint(10, T + 1, (B,), dtype=torch.int32)
+    lens[3] = T
+    return p, lens.cuda(), torch.randn(T, B, K, device="cuda") * 0.3, torch.randn(T, B, 1024, device="cuda") * 0.1
+
+
+def _grads(p, x):
+    out = {n: q.grad.clone() for n, q in p.named_parameters()}
+    out["x"] = x.grad.clone()
+    for q in list(p.parameters()) + [x]:
+        q.grad = None
+    return out
+
+
+def test_decoder_pair_sequential_backward_serves_anomaly_mode_and_both(env, monkeypatch):
+    """DecoderPairFn's sequential backward (FLOWTRON_LSTM_PAIR_BWD=0, the default): image-only mode hands layer 0's dgates to the input
+    projection as the image alone -- a foreign pre-hook sees NaN --, while anomaly mode (check_nan) and FLOWTRON_LSTM_PERSIST_IMG=both get
+    real fp32 values, and all three give the same gradients (bit for bit but the bias sums, whose column sums are fp32 atomics)"""
+    L, ops = env
+    import contextlib
+    T, B = 48, 32
+    if not ops.lstm_persist_groups(B, 1024, False, L.FT_BF16, torch.device("cuda", torch.cuda.current_device())):
+        pytest.skip("persistent recurrences not usable on this device")
+    p, lens, x0, dh = _pair_setup(T, B)
+    monkeypatch.setattr(ops, "_PAIR_CHUNKS_BWD", 0)
+    monkeypatch.setattr(ops, "_GX16", False)                          # (gx as fp32 rows in every mode: bitwise comparison)
+
+    def run(img_mode, anomaly=False):
+        monkeypatch.setattr(ops, "_PERSIST_IMG", img_mode)
+        torch.empty(64 << 20, device="cuda").fill_(7.0)
+        x = x0.clone().requires_grad_(True)
+        seen = []
+        with (torch.autograd.detect_anomaly(check_nan=True) if anomaly else contextlib.nullcontext()):
+            h, _ = ops.decoder_pair(x, lens, p, L.FT_BF16, [], ops.row_map(lens, T, B), "dx", None, 4)
+            lin = h.grad_fn.next_functions[0][0]
+            assert "LinearFn" in type(lin).__name__
+            lin.register_prehook(lambda grads: seen.append(grads[0]))
+            h.backward(dh)
+        torch.cuda.synchronize()
+        ops.check_persist_status()
+        return _grads(p, x), seen[0]
+
+    g_img, seen = run("1")
+    assert bool(torch.isnan(seen).all()), "a foreign reader of an image-only gradient must see NaN"
+    g_both, seen = run("both")
+    assert bool(torch.isfinite(seen).all()), "FLOWTRON_LSTM_PERSIST_IMG=both: the pair must hand real dgates to its consumer"
+    g_anom, seen = run("1", anomaly=True)
+    assert bool(torch.isfinite(seen).all())
+    for other in (g_both, g_anom):
+        for n in g_img:
+            assert torch.isfinite(other[n]).all(), n
+            if "bias" in n:
+                assert rel(other[n], g_img[n]) <= 1e-6, n
+            else:
+                assert torch.equal(other[n], g_img[n]), n
+
+
+@pytest.mark.parametrize("nch_bwd", [0, -1])
+def test_second_backward_through_the_decoder_pair_and_its_projections(env, monkeypatch, nch_bwd):
+    """retain_graph: a second backward through DecoderPairFn and the input projection in front of it (LinearGateFn on [x ; ctx] with the
+    gate layer, as the decoder runs it) returns what the first one returned -- the weight images the first backward released are made again"""
+    L, ops = env
+    import torch.nn as nn
+    T, B, A = 48, 32, 64
+    if not ops.lstm_persist_groups(B, 1024, False, L.FT_BF16, torch.device("cuda", torch.cuda.current_device())):
+        pytest.skip("persistent recurrences not usable on this device")
+    monkeypatch.setattr(ops, "_PAIR_CHUNKS_BWD", nch_bwd)
+    p, lens, x0, dh = _pair_setup(T, B, K=1024 + A)
+    x1 = torch.randn(T, B, 1024, device="cuda") * 0.3
+    cx = (torch.randn(T, B, A, device="cuda") * 0.3).requires_grad_(True)
+    gw, gb = (torch.randn(1, 1024 + A, device="cuda") * 0.02).requires_grad_(True), torch.zeros(1, device="cuda", requires_grad=True)
+    dg = torch.randn(T, B, 1, device="cuda") * 0.1
+    valid = (torch.arange(T, device="cuda")[:, None] < lens[None, :])[..., None].float()
+    x = x1.clone().requires_grad_(True)
+    h, gates = ops.decoder_pair(x, lens, p, L.FT_BF16, [cx], ops.row_map(lens, T, B), "dx", (gw, gb), 4)
+    loss = (h * dh).sum() + (gates * dg * valid).sum()
+    firsts = []
+    for k in range(2):
+        loss.backward(retain_graph=k == 0)
+        torch.cuda.synchronize()
+        ops.check_persist_status()
+        gr = _grads(p, x)
+        gr.update(cx=cx.grad.clone(), gw=gw.grad.clone(), gb=gb.grad.clone())
+        cx.grad = gw.grad = gb.grad = None
+        firsts.append(gr)
+    for n in firsts[0]:
+        assert torch.isfinite(firsts[1][n]).all(), n
+        assert rel(firsts[1][n], firsts[0][n]) <= 1e-6, (n, rel(firsts[1][n], firsts[0][n]))
+
+
+@pytest.mark.parametrize("two_inputs", [False, True])
+def test_second_backward_through_lstm_layer_projection(env, two_inputs):
+    """retain_graph through ops.lstm_layer: LinearFn (one input: per-input compact images; two: the concatenated image) behind an LSTM
+    whose dgates reach it as the image alone -- the second backward makes the forward's images again and returns the same gradients"""
+    L, ops = env
+    T, B, K = 40, 32, 256
+    if not ops.lstm_persist_groups(B, 1024, False, L.FT_BF16, torch.device("cuda", torch.cuda.current_device())):
+        pytest.skip("persistent recurrences not usable on this device")
+    torch.manual_seed(8)
+    lens = torch.tensor([T] * 4 + [max(2, T - i) for i in range(B - 4)], dtype=torch.int32, device="cuda")
+    xs = [(torch.randn(T, B, K, device="cuda") * 0.5).requires_grad_(True) for _ in range(2 if two_inputs else 1)]
+    Kt = K * len(xs)
+    w_ih = (torch.randn(4096, Kt, device="cuda") / Kt ** 0.5).requires_grad_(True)
+    w_hh = (torch.randn(4096, 1024, device="cuda") / 32).requires_grad_(True)
+    b = (torch.randn(4096, device="cuda") * 0.1).requires_grad_(True)
+    h = ops.lstm_layer(xs[0], lens, w_ih, w_hh, b, torch.zeros_like(b), mode=L.FT_BF16, xs_extra=xs[1:], rowmap=ops.row_map(lens, T, B), fill="dx")
+    dh = torch.randn(T, B, 1024, device="cuda") * 0.1
+    out = []
+    for k in range(2):
+        h.backward(dh, retain_graph=k == 0)
+        torch.cuda.synchronize()
+        ops.check_persist_status()
+        ts = [w_ih, w_hh, b] + xs
+        out.append([t.grad.clone() for t in ts])
+        for t in ts:
+            t.grad = None
+    for a, c in zip(*out):
+        assert torch.isfinite(c).all() and rel(c, a) <= 1e-6, rel(c, a)
+
+
+def test_second_backward_through_the_split_image_convolution(env):
+    """the encoder convolution's default 16-bit forward (split images made straight from x; the fp32 column matrix is never written):
+    a second backward (retain_graph) makes the split images again from x -- never from the unwritten column matrix"""
+    L, ops = env
+    Lx, B, C = 61, 8, 512
+    torch.manual_seed(4)
+    lens = torch.tensor([Lx, 1, 40, 17, Lx, 33, 2, 59], dtype=torch.int32, device="cuda")
+    m = (torch.arange(Lx, device="cuda")[:, None] < lens[None, :])[..., None].float()
+    x = (torch.randn(Lx, B, C, device="cuda") * m).requires_grad_(True)
+    w = (torch.randn(C, C, 5, device="cuda") * 0.02).requires_grad_(True)
+    cb = torch.zeros(C, device="cuda", requires_grad=True)
+    gamma, beta = torch.ones(C, device="cuda", requires_grad=True), torch.zeros(C, device="cuda", requires_grad=True)
+    keep = torch.ones(Lx, B, C, device="cuda")
+    y = ops.conv_norm_relu(x, lens, w, cb, gamma, beta, keep, 1e-5, mode=("split3", L.FT_BF16, L.FT_BF16))
+    dy = torch.randn_like(y) * m
+    out = []
+    for k in range(2):
+        y.backward(dy, retain_graph=k == 0)
+        torch.cuda.synchronize()
+        ts = [x, w, gamma, beta]
+        out.append([t.grad.clone() for t in ts])
+        for t in ts:
+            t.grad = None
+    for a, c in zip(*out):
+        assert torch.isfinite(c).all() and rel(c, a) <= 1e-6, rel(c, a)
+
+
+# ---------------------------------------------------------------- ft_bf16_image_split3_im2col (ABI 14)
+@pytest.mark.parametrize("fmt", [1, 2])
+@pytest.mark.parametrize("Lx,B,C,KW", [(37, 7, 512, 5), (50, 3, 8, 5), (23, 5, 16, 3)])
+def test_split3_im2col_image_equals_split3_of_im2col(env, fmt, Lx, B, C, KW):
+    """the split [hi | lo | hi] image made straight from x equals, byte for byte, ft_bf16_image_split3 of ft_im2col(x) -- ragged lens
+    with 1 and L, L B not a multiple of 256 -- and hi + lo widened matches a float64 im2col of the masked x (include/flowtron_hip.h:
+    col[l][b][c KW + k] = x[l + k - KW/2][b][c], 0 outside [0, lens[b])) to 2^-16 relative (fp16: + its subnormal spacing)"""
+    L, ops = env
+    torch.manual_seed(Lx + C + fmt)
+    lens_l = [Lx, 1] + [int(v) for v in torch.randint(1, Lx + 1, (B - 2,))]
+    lens = torch.tensor(lens_l, dtype=torch.int32, device="cuda")
+    m = (torch.arange(Lx, device="cuda")[:, None] < lens[None, :])[..., None].float()
+    x = torch.randn(Lx, B, C, device="cuda") * torch.exp(torch.randn(Lx, B, C, device="cuda") * 2) * m
+    CK, rows = C * KW, Lx * B
+    col = torch.empty(Lx, B, CK, device="cuda")
+    L.check(L.lib().ft_im2col(L.ptr(x), L.ptr(col), L.ptr(lens), Lx, B, C, KW, L.stream()), "ft_im2col")
+    a = ops.Bf16Image.split3(col.reshape(rows, CK), fmt, False)
+    b = ops.Bf16Image.split3_im2col(x, lens, KW, fmt)
+    torch.cuda.synchronize()
+    assert a.ld == b.ld and a.cols == b.cols == 3 * CK
+    dt = torch.float16 if fmt == 2 else torch.bfloat16
+    ia = a.buf[:rows * a.ld * 2].view(dt).reshape(rows, a.ld)[:, :3 * CK]
+    ib = b.buf[:rows * b.ld * 2].view(dt).reshape(rows, b.ld)[:, :3 * CK]
+    assert torch.equal(ia.view(torch.int16), ib.view(torch.int16))
+    # independent reference: float64 im2col by the header's formula
+    xd = x.double()
+    ref = torch.zeros(Lx, B, C, KW, dtype=torch.float64, device="cuda")
+    for k in range(KW):
+        src = torch.arange(Lx, device="cuda") + k - KW // 2
+        ok = ((src[:, None] >= 0) & (src[:, None] < lens[None, :].long()))[..., None].double()
+        ref[:, :, :, k] = xd[src.clamp(0, Lx - 1)] * ok
+    ref = ref.reshape(rows, CK)
+    hi, lo, hi2 = ib[:, :CK].double(), ib[:, CK:2 * CK].double(), ib[:, 2 * CK:].double()
+    assert torch.equal(hi, hi2)
+    assert torch.equal(hi, ref.to(dt).double()), "hi = op16(col)"
+    tol = 2.0 ** -16 * ref.abs() + (2.0 ** -25 if fmt == 2 else 0.0)
+    assert bool(((hi + lo - ref).abs() <= tol).all()), float(((hi + lo - ref).abs() - tol).max())

@@ -2,6 +2,11 @@
 TacotronSTFT.mel_spectrogram as ONE HIP kernel (ft_stft_mel: reflect pad + windowed radix-2 FFT
 in LDS + |X| + mel filterbank + log-compression) instead of a 1026x1024 dense-DFT conv1d.
 
+The synthesis side (audio_processing.py:7-75, 237-270) is here too: STFT.inverse / STFT.forward run
+the inverse real FFT + overlap-add kernel ft_istft_r8, `griffin_lim` loops it with ft_stft_r8 on the
+device, and `window_sumsquare` is the reference's host function.  TacotronSTFT.mel_to_magnitude /
+mel_to_audio (not in the reference) turn model output into a waveform.
+
 The mel filterbank constants come from librosa in the reference (third-party dependency that is
 not vendored: requirements.txt:4 pins 0.6.3, Dockerfile:6 pins 0.8.0; call site
 audio_processing.py:104-105 -> htk=False, Slaney area normalisation).  librosa is not installed
@@ -16,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .ops import gemm_raw
 
 
 def _hz_to_mel(f):
@@ -57,7 +63,7 @@ def slaney_mel_filterbank(sr, n_fft, n_mels, fmin=0.0, fmax=None) -> np.ndarray:
     return (w * enorm[:, None]).astype(np.float32)
 
 
-def hann_window(win_length: int, filter_length: int) -> np.ndarray:
+def hann_window(win_length: int, filter_length: int, dtype=np.float32) -> np.ndarray:
     """scipy.signal.get_window('hann', win_length, fftbins=True) zero-centre-padded to filter_length
     (audio_processing.py:193-197)."""
     n = np.arange(win_length, dtype=np.float64)
@@ -65,7 +71,45 @@ def hann_window(win_length: int, filter_length: int) -> np.ndarray:
     lpad = (filter_length - win_length) // 2
     out = np.zeros(filter_length, dtype=np.float64)
     out[lpad:lpad + win_length] = w
-    return out.astype(np.float32)
+    return out.astype(dtype)
+
+
+def window_sumsquare(window, n_frames, hop_length=200, win_length=800, n_fft=800, dtype=np.float32, norm=None):
+    """audio_processing.py:7-56 (librosa 0.6): the sum-square envelope of the window at this hop, shape
+    [n_fft + hop_length * (n_frames - 1)], on the host.  Only the hann window without normalisation (what STFT uses)."""
+    if not (isinstance(window, str) and window == "hann"):
+        raise NotImplementedError("window_sumsquare supports window='hann' only, got %r" % (window,))
+    if norm is not None:
+        raise NotImplementedError("window_sumsquare supports norm=None only, got %r" % (norm,))
+    if win_length is None:
+        win_length = n_fft
+    n = n_fft + hop_length * (n_frames - 1)
+    x = np.zeros(n, dtype=dtype)
+    win_sq = hann_window(win_length, n_fft, dtype=np.float64) ** 2
+    for i in range(n_frames):
+        sample = i * hop_length
+        x[sample:min(n, sample + n_fft)] += win_sq[:max(0, min(n_fft, n - sample))]
+    return x
+
+
+def griffin_lim(magnitudes, stft_fn, n_iters=30):
+    """audio_processing.py:59-75 on the device.  magnitudes [B, n_fft/2+1, T] (device tensor), stft_fn an STFT.
+    The starting angles are drawn on the host exactly as the reference draws them (np.random.rand, so np.random.seed(s)
+    gives the reference's starting point) and copied to the device once; then n_iters x (ft_stft_r8 for the phase +
+    ft_istft_r8) run without a host synchronisation.  Returns [B, hop * (T - 1)]."""
+    L.require_cuda(magnitudes)
+    stft_fn._check_spectrum(magnitudes, magnitudes)
+    T = magnitudes.shape[-1]
+    if stft_fn.hop_length * (T - 1) <= stft_fn.filter_length // 2:
+        raise ValueError("griffin_lim needs hop * (T - 1) > filter_length / 2 samples for the reflect padding of STFT.transform; "
+                         "got T = %d frames at hop %d" % (T, stft_fn.hop_length))
+    angles = np.angle(np.exp(2j * np.pi * np.random.rand(*magnitudes.size())))
+    angles = torch.from_numpy(angles.astype(np.float32)).to(magnitudes.device)
+    signal = stft_fn.inverse(magnitudes, angles).squeeze(1)
+    for _ in range(n_iters):
+        _, angles = stft_fn.transform(signal)
+        signal = stft_fn.inverse(magnitudes, angles).squeeze(1)
+    return signal
 
 
 def dynamic_range_compression(x, C=1, clip_val=1e-5):
@@ -93,8 +137,9 @@ def filterbank_csr(mel_basis: np.ndarray):
 
 
 class STFT(torch.nn.Module):
-    """Analysis half of the reference STFT (audio_processing.py:172-235): `transform(y)` -> (magnitude, phase), both
-    [B, n_fft/2+1, N // hop + 1], one HIP kernel (real FFT, csrc/stft_r8.hip).  The inverse (Griffin-Lim side) is out of scope."""
+    """The reference STFT (audio_processing.py:172-270): `transform(y)` -> (magnitude, phase), both [B, n_fft/2+1, N // hop + 1]
+    (real FFT, ft_stft_r8), `inverse(magnitude, phase)` -> [B, 1, hop * (T - 1)] (inverse real FFT + overlap-add, ft_istft_r8)
+    and `forward(y)` = inverse(transform(y)); one HIP kernel each (csrc/stft_r8.hip)."""
 
     def __init__(self, filter_length=800, hop_length=200, win_length=800, window="hann"):
         super().__init__()
@@ -121,6 +166,33 @@ class STFT(torch.nn.Module):
                                    self.hop_length, 0, L.stream()), "ft_stft_r8")
         return mag, phase
 
+    def _check_spectrum(self, magnitude, phase):
+        if not self.fast_path():
+            raise NotImplementedError("STFT.inverse is built for filter_length 1024 / hop <= 256 (config.json:32-34)")
+        nb = self.filter_length // 2 + 1
+        if magnitude.dim() != 3 or magnitude.shape[1] != nb or phase.shape != magnitude.shape:
+            raise ValueError("STFT.inverse needs magnitude and phase of one shape [B, %d, T], got %s and %s"
+                             % (nb, tuple(magnitude.shape), tuple(phase.shape)))
+
+    def inverse(self, magnitude, phase):
+        """audio_processing.py:237-263: [B, n_fft/2+1, T] x 2 -> [B, 1, hop * (T - 1)] (ft_istft_r8)."""
+        L.require_cuda(magnitude, phase)
+        self._check_spectrum(magnitude, phase)
+        m, ph = magnitude.contiguous().float(), phase.contiguous().float()
+        if self.fft_window.device != m.device:
+            self.to(m.device)
+        B, _, T = m.shape
+        y = torch.empty(B, 1, self.hop_length * max(T - 1, 0), device=m.device, dtype=torch.float32)
+        if T >= 2:                                      # one frame leaves nothing after the two 512-sample trims
+            L.check(L.lib().ft_istft_r8(L.ptr(m), L.ptr(ph), L.ptr(self.fft_window), L.ptr(y), B, T, self.hop_length,
+                                        L.stream()), "ft_istft_r8")
+        return y
+
+    def forward(self, input_data):
+        """audio_processing.py:265-268."""
+        self.magnitude, self.phase = self.transform(input_data)
+        return self.inverse(self.magnitude, self.phase)
+
 
 class TacotronSTFT(torch.nn.Module):
     def __init__(self, filter_length=1024, hop_length=256, win_length=1024, n_mel_channels=80, sampling_rate=22050,
@@ -135,6 +207,9 @@ class TacotronSTFT(torch.nn.Module):
         self.register_buffer("fb_bin0", torch.from_numpy(bin0), persistent=False)
         self.register_buffer("fb_ptr", torch.from_numpy(ptr), persistent=False)
         self.register_buffer("fb_w", torch.from_numpy(w), persistent=False)
+        # pseudo-inverse of the filterbank for mel_to_magnitude, in float64 once (not in the state_dict)
+        self.register_buffer("mel_pinv", torch.from_numpy(np.linalg.pinv(basis.astype(np.float64)).astype(np.float32)),
+                             persistent=False)
 
     def spectral_normalize(self, magnitudes):
         return dynamic_range_compression(magnitudes)
@@ -184,3 +259,32 @@ class TacotronSTFT(torch.nn.Module):
             L.check(L.lib().ft_stft_mel(L.ptr(y), L.ptr(st.fft_window), L.ptr(self.mel_basis), L.ptr(mel), B, N,
                                         st.filter_length, st.hop_length, self.n_mel_channels, L.stream()), "ft_stft_mel")
         return mel
+
+    def mel_to_magnitude(self, mel):
+        """Addition, not in the reference: log-mel [B, n_mel, T] (or [n_mel, T]) -> linear magnitudes [B, n_fft/2+1, T]
+        (or [n_fft/2+1, T]) = relu(pinv(mel_basis) @ spectral_de_normalize(mel)), the product on ft_gemm in fp32 with the
+        ReLU epilogue, one batched call.  Frames after an utterance's end that hold zeros decode as magnitude 1, not
+        silence: trim each utterance to its own length first (ragged batches are not supported)."""
+        L.require_cuda(mel)
+        if mel.dim() not in (2, 3) or mel.shape[-2] != self.n_mel_channels:
+            raise ValueError("mel_to_magnitude needs [B, %d, T] or [%d, T], got %s"
+                             % (self.n_mel_channels, self.n_mel_channels, tuple(mel.shape)))
+        if self.mel_pinv.device != mel.device:
+            self.to(mel.device)
+        x = self.spectral_de_normalize(mel.float()).contiguous()
+        x3 = x if x.dim() == 3 else x[None]
+        B, n_mel, T = x3.shape
+        nb = self.mel_pinv.shape[0]
+        out = torch.empty(B, nb, T, device=mel.device, dtype=torch.float32)
+        gemm_raw(self.mel_pinv, x3, out, nb, T, n_mel, n_mel, 1, T, 1, T, act=L.ACT_RELU, batch=B, bsA=0, bsB=n_mel * T,
+                 bsC=nb * T, mode=L.FT_F32)
+        return out if mel.dim() == 3 else out[0]
+
+    def mel_to_audio(self, mel, n_iters=30):
+        """Addition, not in the reference: log-mel [B, n_mel, T] (a dense batch, e.g. Flowtron.infer's output) or [n_mel, T]
+        -> waveform [B, hop * (T - 1)] (or [hop * (T - 1)]) = griffin_lim(mel_to_magnitude(mel), self.stft_fn, n_iters).
+        Every utterance of a batch must fill all T frames: trim padded or post-stop frames before vocoding (zeros decode as
+        magnitude 1, not silence)."""
+        mag = self.mel_to_magnitude(mel)
+        y = griffin_lim(mag if mag.dim() == 3 else mag[None], self.stft_fn, n_iters)
+        return y if mel.dim() == 3 else y[0]

@@ -14,6 +14,8 @@
 //     per frame = 1 344 B of HBM traffic.
 #include "common.h"
 
+#include <cfloat>
+
 namespace {
 
 constexpr int NFFT = 1024, NH = 512, NB = 513;
@@ -40,6 +42,55 @@ __device__ __forceinline__ void dft8(cpx (&v)[8]) {
     v[1] = cadd(b1, b5); v[5] = csub(b1, b5);
     v[2] = cadd(b2, b6); v[6] = csub(b2, b6);
     v[3] = cadd(b3, b7); v[7] = csub(b3, b7);
+}
+
+// The per-lane twiddle constants of fft512_r8 and the split step depend on (lane, k) only; a workgroup evaluates each once into
+// LDS (1 152 sincospif over 256 threads): tw[0, 512) = W512^{l k}, tw[512, 576) = W64^{b k}, tw[576, 1152) = W1024^{k}.
+__device__ __forceinline__ void fill_twiddles(cpx* tw, int tid) {
+    for (int i = tid; i < 512 + 64 + 576; i += 256) {
+        float s, c, a;
+        if (i < 512) a = (float)((i >> 3) * (i & 7)) / 512.0f;
+        else if (i < 576) a = (float)(((i - 512) >> 3) * ((i - 512) & 7)) / 64.0f;
+        else a = (float)(i - 576) / 1024.0f;
+        sincospif(-2.0f * a, &s, &c);
+        tw[i] = (cpx){c, s};
+    }
+}
+
+// 512-point forward DFT held by one wave: on entry lane l holds v[j] = z[l + 64 j]; on exit v[k3] = Z[k1 + 8 k2 + 64 k3] with
+// (k1, k2) = (lane >> 3, lane & 7).  Three radix-8 passes (n = 64 j + 8 a + b: DFT_8 over j, twiddle w1 = W512^{l k1}, transpose
+// through LDS, DFT_8 over a, twiddle w2 = W64^{b k2}, transpose, DFT_8 over b).  T: the wave's own 512-entry LDS buffer; the
+// LDS operations of one wave execute in order, so no barrier is needed.
+__device__ __forceinline__ void fft512_r8(cpx (&v)[8], cpx* T, const cpx (&w1)[8], const cpx (&w2)[8], int lane) {
+    dft8(v);
+#pragma unroll
+    for (int k = 1; k < 8; ++k) v[k] = cmul(v[k], w1[k]);
+    // transpose 1: element (l = 8 a + b2, k1) -> lane (k1, b2), register a
+    {
+        const int a = lane >> 3, b2 = lane & 7;
+#pragma unroll
+        for (int k1 = 0; k1 < 8; ++k1) T[(k1 * 8 + b2) * 8 + a] = v[k1];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int a = 0; a < 8; ++a) v[a] = T[lane * 8 + a];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // pass 2: DFT over a; twiddle W64^{b2 k2}
+    dft8(v);
+#pragma unroll
+    for (int k = 1; k < 8; ++k) v[k] = cmul(v[k], w2[k]);
+    // transpose 2: element (k1, b2, k2) -> lane (k1, k2), register b2
+    {
+        const int k1 = lane >> 3, b2 = lane & 7;
+#pragma unroll
+        for (int k2 = 0; k2 < 8; ++k2) T[(k1 * 8 + k2) * 8 + b2] = v[k2];
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int b2 = 0; b2 < 8; ++b2) v[b2] = T[lane * 8 + b2];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    // pass 3: DFT over b2
+    dft8(v);
 }
 
 struct StftP {
@@ -100,15 +151,8 @@ __global__ __launch_bounds__(256) void stft_r8_k(StftP p) {
     cpx w1[8], w2[8], w3[9];
     float2 win[8];
     {
-        cpx* tw = &tr[0][0];                                              // [0, 512): W512^{l k}; [512, 576): W64^{b k}; [576, 1152): W1024^{k}
-        for (int i = tid; i < 512 + 64 + 576; i += 256) {
-            float s, c, a;
-            if (i < 512) a = (float)((i >> 3) * (i & 7)) / 512.0f;
-            else if (i < 576) a = (float)(((i - 512) >> 3) * ((i - 512) & 7)) / 64.0f;
-            else a = (float)(i - 576) / 1024.0f;
-            sincospif(-2.0f * a, &s, &c);
-            tw[i] = (cpx){c, s};
-        }
+        cpx* tw = &tr[0][0];
+        fill_twiddles(tw, tid);
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -126,7 +170,7 @@ __global__ __launch_bounds__(256) void stft_r8_k(StftP p) {
         const int t = f0 + wave * FPW + fi;
         if (t >= nfb) break;                                              // wave-uniform
         const float* xf = xs + (wave * FPW + fi) * p.hop;
-        // ---- pass 1: lane l holds z[l + 64 j]; DFT over j; twiddle W512^{l k1}
+        // ---- lane l holds z[l + 64 j]; 512-point FFT -> Z[k], k = k1 + 8 k2 + 64 k3 with (k1, k2) = (lane >> 3, lane & 7)
         cpx v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -134,35 +178,7 @@ __global__ __launch_bounds__(256) void stft_r8_k(StftP p) {
             const float2 x2 = *reinterpret_cast<const float2*>(xf + 2 * m);
             v[j] = (cpx){x2.x * win[j].x, x2.y * win[j].y};
         }
-        dft8(v);
-#pragma unroll
-        for (int k = 1; k < 8; ++k) v[k] = cmul(v[k], w1[k]);
-        // transpose 1: element (l = 8 a + b2, k1) -> lane (k1, b2), register a
-        {
-            const int a = lane >> 3, b2 = lane & 7;
-#pragma unroll
-            for (int k1 = 0; k1 < 8; ++k1) T[(k1 * 8 + b2) * 8 + a] = v[k1];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int a = 0; a < 8; ++a) v[a] = T[lane * 8 + a];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // ---- pass 2: DFT over a; twiddle W64^{b2 k2}
-        dft8(v);
-#pragma unroll
-        for (int k = 1; k < 8; ++k) v[k] = cmul(v[k], w2[k]);
-        // transpose 2: element (k1, b2, k2) -> lane (k1, k2), register b2
-        {
-            const int k1 = lane >> 3, b2 = lane & 7;
-#pragma unroll
-            for (int k2 = 0; k2 < 8; ++k2) T[(k1 * 8 + k2) * 8 + b2] = v[k2];
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int b2 = 0; b2 < 8; ++b2) v[b2] = T[lane * 8 + b2];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        // ---- pass 3: DFT over b2 -> Z[k], k = k1 + 8 k2 + 64 k3 with (k1, k2) = (lane >> 3, lane & 7)
-        dft8(v);
+        fft512_r8(v, T, w1, w2, lane);
         {
             const int q = (lane >> 3) + 8 * (lane & 7);
 #pragma unroll
@@ -255,6 +271,161 @@ extern "C" int ft_stft_r8_ragged(const float* y, const int32_t* n_samples, const
     FT_CHECK_ARG(B >= 1 && B <= 65535 && hop >= 1 && hop <= 256 && N > NH && T_out >= 1);
     StftP p{y, window, band_bin0, band_ptr, band_w, mel, nullptr, nullptr, N, hop, n_mel, T_out, n_samples, T_out};
     hipLaunchKernelGGL(stft_r8_k, dim3(cdiv(T_out, FPG), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
+    FT_CHECK_LAUNCH();
+    return FT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Inverse STFT (audio_processing.py:237-263, STFT.inverse) for the same setting: (magnitude, phase) [B,513,T] -> y [B,hop*(T-1)],
+//
+//   y[n] = sum_t  w[u - t hop] irfft(X_t)[u - t hop] / wss[u]   (only where wss[u] > FLT_MIN),   u = n + 512,
+//   wss[u] = sum_t w^2[u - t hop],   X_t[k] = M[k,t] e^{i phase[k,t]}
+//
+// which is what the reference's conv_transpose1d with pinv(scale F)^T * window, the window_sumsquare division, the scale and the
+// 512-sample trims compute (the pseudo-inverse of the half-spectrum DFT basis is irfft: Im X[0] and Im X[512] are ignored).
+//   * irfft-1024 = ONE 512-point complex inverse FFT plus the inverse split step: with X' = conj X[512 - k],
+//       Z[k] = (X[k] + X') + i e^{+2 pi i k / 1024} (X[k] - X'),   z = IFFT_512(Z) / 2,   x[2m] = Re z[m], x[2m+1] = Im z[m];
+//     the IFFT is fft512_r8 on conj Z, conjugated back (one wave per frame, as in the forward kernel).
+//   * overlap-add without atomics: a workgroup owns 16 hop consecutive output samples and computes every frame that covers
+//     them, its neighbours' halo frames included (ceil(1024 / hop) - 1 of them: 3 of 19 at hop 256).  The windowed frames go
+//     to LDS FC at a time, then each thread adds them into its samples' registers in ascending t -- fixed order, so the result
+//     does not depend on the launch.  No workgroup waits for another.
+//   * 256 threads, 53 KB of LDS, 234 VGPRs without spills: two workgroups per CU (two waves per SIMD, as the forward kernel);
+//     three would need <= 168 VGPRs, and at that budget the compiler spills.
+namespace {
+
+constexpr int FC = 8;                                  // frames staged in LDS per round: 2 per wave
+constexpr int SPT = 16;                                // owned samples per thread: 16 hop <= 4 096 = 256 threads x 16
+
+struct IstftP {
+    const float* mag; const float* phase; const float* window;
+    float* y;
+    int T, hop, n_out;
+};
+
+__global__ __launch_bounds__(256) void istft_r8_k(IstftP p) {
+    __shared__ __attribute__((aligned(16))) float fr[FC][NFFT];          // windowed irfft of the round's frames
+    __shared__ __attribute__((aligned(16))) cpx tr[4][NH + 1];           // per-wave spectrum / transpose buffer
+    __shared__ float wl[NFFT];                                            // the window (for wss)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, hop = p.hop, T = p.T;
+    const int S = 16 * hop;
+    const int n0 = blockIdx.x * S;
+    const int u0 = n0 + NH, u1 = min(n0 + S, p.n_out) + NH;              // untrimmed sample range [u0, u1) of this workgroup
+    const int t_lo = u0 - (NFFT - 1) <= 0 ? 0 : (u0 - (NFFT - 1) + hop - 1) / hop;
+    const int t_hi = min(T - 1, (u1 - 1) / hop);                          // frames t_lo .. t_hi cover [u0, u1)
+    // per-lane constants: w1 = W512^{l k1}, w2 = W64^{b2 k2}, w3[j] = W1024^{k} of the lane's bins k = lane + 64 j, and the window
+    // taps of the lane's 8 output pairs (2m, 2m + 1), m = q + 64 k3
+    const int q = (lane >> 3) + 8 * (lane & 7);
+    cpx w1[8], w2[8], w3[8];
+    float2 win[8];
+    {
+        cpx* tw = &tr[0][0];
+        fill_twiddles(tw, tid);
+        for (int i = tid; i < NFFT; i += 256) wl[i] = p.window[i];
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            w1[k] = tw[lane * 8 + k];
+            w2[k] = tw[512 + (lane & 7) * 8 + k];
+            w3[k] = tw[576 + lane + 64 * k];
+            win[k] = *reinterpret_cast<const float2*>(wl + 2 * (q + 64 * k));
+        }
+    }
+    __syncthreads();
+    float acc[SPT];
+#pragma unroll
+    for (int i = 0; i < SPT; ++i) acc[i] = 0.f;
+    cpx* X = tr[wave];
+    const float* magb = p.mag + (size_t)b * NB * T;
+    const float* phb = p.phase + (size_t)b * NB * T;
+    for (int c0 = t_lo; c0 <= t_hi; c0 += FC) {
+        for (int f = wave; f < FC; f += 4) {
+            const int t = c0 + f;
+            if (t > t_hi) break;                                          // wave-uniform
+            // ---- X[k] = M e^{i phase}, k = lane + 64 j, and k = 512 on lane 0; Im X[0] and Im X[512] dropped (irfft ignores them).
+            // The raw (M, phase) pairs are parked in X first so that all loads are in flight together while the accurate
+            // sincosf (full range reduction, many registers) runs one bin at a time.
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const size_t o = (size_t)(lane + 64 * j) * T + t;
+                X[lane + 64 * j] = (cpx){magb[o], phb[o]};
+            }
+            if (lane == 0) X[NH] = (cpx){magb[(size_t)NH * T + t], phb[(size_t)NH * T + t]};
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll 1
+            for (int k = lane; k <= NH; k += 64) {
+                const cpx mp = X[k];
+                float s, c;
+                sincosf(mp.im, &s, &c);
+                X[k] = (cpx){mp.re * c, (k & (NH - 1)) == 0 ? 0.f : mp.re * s};
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            // ---- inverse split: conj Z[k] for k = lane + 64 j (the input layout of fft512_r8)
+            cpx v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int k = lane + 64 * j;
+                const cpx a = X[k], c = X[NH - k];
+                const cpx s = {a.re + c.re, a.im - c.im};                                // X[k] + conj X[512-k]
+                const cpx d = {a.re - c.re, a.im + c.im};                                // X[k] - conj X[512-k]
+                const cpx e = cmul((cpx){w3[j].re, -w3[j].im}, d);                      // e^{+2 pi i k / 1024} d
+                v[j] = (cpx){s.re - e.im, -(s.im + e.re)};                               // conj(s + i e)
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            fft512_r8(v, X, w1, w2, lane);
+            // ---- v[k3] = conj(2 * 512 z[m]), m = q + 64 k3: x[2m] = Re, x[2m+1] = -Im, scaled by 1/1024 (exact) and windowed
+            float* F = fr[f];
+#pragma unroll
+            for (int k3 = 0; k3 < 8; ++k3) {
+                const int m = q + 64 * k3;
+                *reinterpret_cast<float2*>(F + 2 * m) =
+                    make_float2(win[k3].x * (v[k3].re * (1.0f / 1024.0f)), win[k3].y * (-v[k3].im * (1.0f / 1024.0f)));
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
+        __syncthreads();
+        // ---- overlap-add of this round's frames, ascending t
+        const int nf = min(FC, t_hi - c0 + 1);
+        for (int f = 0; f < nf; ++f) {
+            const int m0 = u0 + tid - (c0 + f) * hop;
+#pragma unroll
+            for (int i = 0; i < SPT; ++i) {
+                const int m = m0 + 256 * i;
+                if (m >= 0 && m < NFFT && u0 + tid + 256 * i < u1) acc[i] += fr[f][m];
+            }
+        }
+        __syncthreads();
+    }
+    // ---- divide by the window's sum-square envelope where it is > FLT_MIN (the reference's tiny(float32) rule), store
+    float* yb = p.y + (size_t)b * p.n_out;
+#pragma unroll
+    for (int i = 0; i < SPT; ++i) {
+        const int u = u0 + tid + 256 * i;
+        if (u < u1) {
+            const int ta = u - (NFFT - 1) <= 0 ? 0 : (u - (NFFT - 1) + hop - 1) / hop, tb = min(T - 1, u / hop);
+            float wss = 0.f;
+            for (int t = ta; t <= tb; ++t) {
+                const float w = wl[u - t * hop];
+                wss += w * w;
+            }
+            yb[u - NH] = wss > FLT_MIN ? acc[i] / wss : acc[i];
+        }
+    }
+}
+
+}  // namespace
+
+// (mag, phase) [B,513,T] -> y [B, hop (T-1)]: STFT.inverse (audio_processing.py:237-263) for n_fft = 1024, hop <= 256;
+// window: hann [1024] (win_length zero-padded by the caller), as ft_stft_r8.
+extern "C" int ft_istft_r8(const float* mag, const float* phase, const float* window, float* y, int B, int T, int hop,
+                           void* stream) {
+    FT_CHECK_ARG(mag && phase && window && y);
+    FT_CHECK_ARG(B >= 1 && B <= 65535 && hop >= 1 && hop <= 256 && T >= 2);
+    FT_CHECK_ARG((int64_t)hop * (T - 1) <= INT32_MAX - 2 * NFFT);
+    const int n_out = hop * (T - 1);
+    IstftP p{mag, phase, window, y, T, hop, n_out};
+    hipLaunchKernelGGL(istft_r8_k, dim3(cdiv(n_out, 16 * hop), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
     FT_CHECK_LAUNCH();
     return FT_OK;
 }

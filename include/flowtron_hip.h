@@ -516,6 +516,11 @@ int ft_stft_r8(const float* y, const float* window, const int32_t* band_bin0, co
 int ft_stft_r8_ragged(const float* y, const int32_t* n_samples, const float* window, const int32_t* band_bin0,
                       const int32_t* band_ptr, const float* band_w, float* mel, int B, int N, int hop, int n_mel, int T_out,
                       void* stream);
+/* Inverse STFT (audio_processing.py:237-263, STFT.inverse) for the same setting n_fft = 1024, hop <= 256: (mag, phase) [B,513,T]
+ * -> y [B, hop (T-1)] = the windowed irfft of every frame M e^{i phase} (Im of bins 0 and 512 ignored), overlap-added, divided by
+ * the window's sum-square envelope where that is > FLT_MIN, first and last 512 samples cut.  Deterministic: no atomics, each
+ * sample sums its frames in ascending t.  window: hann [1024] as ft_stft_r8.  T >= 2. */
+int ft_istft_r8(const float* mag, const float* phase, const float* window, float* y, int B, int T, int hop, void* stream);
 
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with

@@ -75,6 +75,10 @@ class DecodeArgs(C.Structure):
                                                                                          ("n_layers", _i), ("extra_layers", _p)]
 
 
+class DecodeBatchArgs(C.Structure):
+    _fields_ = [("a", DecodeArgs), ("nb", _i), ("n_lim", _p), ("wimg_ready", _i)]
+
+
 SUMSQ_PARTIALS = 1024      # FT_SUMSQ_PARTIALS: floats of scratch ft_sumsq needs
 
 # name -> argtypes (every symbol include/flowtron_hip.h declares; checked by tests/test_host_cpu.py)
@@ -164,6 +168,9 @@ SIGNATURES = {
     "ft_decode_persist_gran_bytes": ([], _sz),
     "ft_decode_debug_prof": ([_p], _i),
     "ft_decode_flow": ([C.POINTER(DecodeArgs), _p], _i),
+    "ft_decode_batch_max": ([], _i),
+    "ft_decode_batch_gran_bytes": ([_i], _sz),
+    "ft_decode_flow_batch": ([C.POINTER(DecodeBatchArgs), _p], _i),
     "ft_stft_mel": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "ft_stft_r8": ([_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
     "ft_stft_r8_ragged": ([_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),

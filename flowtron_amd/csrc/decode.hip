@@ -25,36 +25,8 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
+#include "decode_dev.h"
 
-struct DecodeDev {
-    const float *att_w_ih, *att_w_hh, *att_b_ih, *att_b_hh;
-    const float *w_query, *v, *K, *V;
-    const float *l0_w_ih, *l0_w_hh, *l0_b_ih, *l0_b_hh, *l1_w_ih, *l1_w_hh, *l1_b_ih, *l1_b_hh;
-    const float *d0_w, *d0_b, *d1_w, *d1_b, *conv_w, *conv_b, *gate_w, *gate_b;
-    const float* residual; float* mel_out; float* attn_out; int* n_done_dev;
-    float *h_att, *c_att, *h0, *c0, *h1, *c1;   // h_*: [2][H] ping-pong by frame parity
-    float *q, *ctx, *u1, *u2, *prev;
-    // cumulative (location-sensitive) attention, flowtron.py:129-152, :793-806 -- all null when use_cumm_attention is off
-    const float *cond_w1, *cond_b1, *cond_w2, *cond_b2, *w_key, *enc;
-    const float *prior, *forced;                 // [N,L] attention prior (posterior, flowtron.py:544-557) / forced alignment (:585-588)
-    float *cumm, *prev_attn, *keyin, *Kdyn;
-    float *escore, *obuf;                        // attention scores [L], 1x1 conv output [2M] (stage hand-offs)
-    int* ctl;                                    // [0] frame index, [1] done flag
-    // bf16 images of the weight matrices (null = stream the fp32 originals)
-    const bf16_t *att_w_ih16, *att_w_hh16, *w_query16, *l0_w_ih16, *l0_w_hh16, *l1_w_ih16, *l1_w_hh16, *d0_w16, *d1_w16, *conv_w16;
-    int N, L, H, A, M, E;
-    float inv_temp, gate_threshold;
-};
-
-// ---- bf16 weight images (bf16 operand mode): every weight matrix of the flow is rounded ONCE per ft_decode_flow call into a
-// bf16 copy (53.7 MB instead of 107.4 MB per frame and flow; the copy stays in the Infinity Cache across frames) and the
-// GEMVs stream those; activations and accumulation stay fp32.  16-byte loads = 8 weights per lane.
-__device__ __forceinline__ float dot8(const uint4 w, const float4 xa, const float4 xb) {
-    return __uint_as_float(w.x << 16) * xa.x + __uint_as_float(w.x & 0xffff0000u) * xa.y + __uint_as_float(w.y << 16) * xa.z +
-           __uint_as_float(w.y & 0xffff0000u) * xa.w + __uint_as_float(w.z << 16) * xb.x + __uint_as_float(w.z & 0xffff0000u) * xb.y +
-           __uint_as_float(w.w << 16) * xb.z + __uint_as_float(w.w & 0xffff0000u) * xb.w;
-}
 // one weight row against an fp32 activation segment; K % 8 == 0, 16-byte aligned (checked by the host for the bf16 path)
 __device__ __forceinline__ float dot_seg(const bf16_t* __restrict__ w, const float* __restrict__ x, int K, int lane) {
     const uint4* w8 = reinterpret_cast<const uint4*>(w);
@@ -439,204 +411,7 @@ __global__ __launch_bounds__(256) void dec_fin_k(const DecodeDev P) {
 //   position(s) c (+256 ..) of the scores, context channels {c, c+256, c+512} and row c of the 1x1 conv.
 // Hops per frame: o -> S1 (inverse coupling of the previous frame + attention LSTM), h_att -> S2 (query), q -> S3a (scores),
 // scores -> S3b (softmax + context), ctx -> S4 (gate, LSTM 0), h0 -> S5 (LSTM 1), h1 -> S6, u1 -> S7, u2 -> S8 (conv).
-struct DecP {
-    DecodeDev d;
-    unsigned long long* gran;     // granule buffers, one per stage vector (offsets below, in granules)
-    unsigned* census;             // 8 counters behind the nine granule copies (zeroed with them)
-    int* status;
-    long timeout_ticks;
-    long* prof;                   // debug: [frame][12] wall-clock stamps of workgroup 0 (ft_decode_debug_prof), or null
-};
-enum { G_O = 0, G_HATT = 256, G_Q = 256 + 1024, G_SC = G_Q + 640, G_CTX = G_SC + 1024, G_H0 = G_CTX + 640, G_H1 = G_H0 + 1024,
-       G_U1 = G_H1 + 1024, G_U2 = G_U1 + 1024, G_TOTAL = G_U2 + 1024 };
-
-typedef __attribute__((address_space(1))) unsigned long long dgu64;
-typedef __attribute__((ext_vector_type(4))) unsigned int du32x4;
-constexpr int DEC_LAUX = 2;         // aux bits of the XCD-local gather loads: 2 = nt (as lstm_persist.hip's default), 16 = sc1
-
-__device__ __forceinline__ void publish(unsigned long long* g, unsigned epoch, float v) {
-    __hip_atomic_store((dgu64*)g, ((unsigned long long)epoch << 32) | __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// into this XCD's copy: stays in its L2
-__device__ __forceinline__ void publish_local(unsigned long long* g, unsigned epoch, float v) {
-    __hip_atomic_store((dgu64*)g, ((unsigned long long)epoch << 32) | __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// Hand-off topology.  256 workgroups each polling a whole vector across the fabric is 2 MB of sc1 reads per pass -- measured,
-// that contention (not the weight stream) is what a stage costs: ~3.5 us per hop against 0.63 us for a lone poller
-// (scripts/exp/handoff_probe.hip).  So every vector crosses the fabric ONCE PER XCD: the 32 workgroups of an XCD (run-time census,
-// as lstm_persist.hip) each relay a 1/32 slice from the global copy (sc1 polls, 16 lanes) into their XCD's own copy with
-// workgroup-scope stores that stay in that XCD's L2, and all of them gather the whole vector from the local copy (~0.25 us).
-// Tags travel with the data, so a granule is only ever forwarded / consumed when it shows the epoch: no fences anywhere.
-struct Relay {
-    unsigned long long* glob;     // p.gran: the producers' copy (write-through stores)
-    unsigned long long* loc;      // this XCD's copy
-    int q;                        // rank of this workgroup inside its XCD, 0..31
-};
-
-// all 256 threads: granules [0, n) of stage vector `off` (epoch-tagged, n <= 1024) -> dst[0, n) in LDS.  false = timed out.
-// Granules [0, relay_lo) were produced INSIDE this XCD (stages every XCD computes for itself, below); [relay_lo, n) come from
-// the chip-wide producers through the relay (relay_lo even).
-__device__ __forceinline__ bool gather(const Relay& R, int off, int n, int relay_lo, unsigned epoch, float* dst, const DecP& p, long t_start) {
-    const int npad = (n + 1) & ~1;
-    bool ok_all = true;
-    if (relay_lo < n) {   // ---- relay: slice q of [relay_lo, n) of the global copy -> local copy; lane pairs of wave 0
-        const int S = 2 * ((n - relay_lo + 63) >> 6);
-        const int j = relay_lo + R.q * S + 2 * (int)threadIdx.x;
-        if ((int)threadIdx.x * 2 < S && j < n) {
-            __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(R.glob + off, 0, npad * 8, 0x00020000);
-            for (unsigned spins = 0;; ++spins) {
-                const du32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rg, j * 8, 0, 16);        // sc1: two granules
-                if (v[1] == epoch && (j + 1 >= n || v[3] == epoch)) {
-                    __hip_atomic_store((dgu64*)(R.loc + off + j), ((unsigned long long)v[1] << 32) | v[0], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (j + 1 < n)
-                        __hip_atomic_store((dgu64*)(R.loc + off + j + 1), ((unsigned long long)v[3] << 32) | v[2], __ATOMIC_RELAXED,
-                                           __HIP_MEMORY_SCOPE_WORKGROUP);
-                    break;
-                }
-                if ((spins & 63) == 63 && (wall_clock64() - t_start > p.timeout_ticks ||
-                                           __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-                    ok_all = false;
-                    break;
-                }
-                asm volatile("" ::: "memory");
-            }
-        }
-    }
-    // ---- gather from the XCD-local copy: a thread owns granule pairs 2 tid and 2 tid + 512, re-reads both while stale
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(R.loc + off, 0, npad * 8, 0x00020000);
-    const int j0 = threadIdx.x * 2, j1 = j0 + 512;
-    bool need0 = j0 < n, need1 = j1 < n;
-    for (unsigned spins = 0; ok_all && (need0 | need1); ++spins) {
-        du32x4 v0, v1;
-        if (need0) v0 = __builtin_amdgcn_raw_buffer_load_b128(rs, j0 * 8, 0, DEC_LAUX);
-        if (need1) v1 = __builtin_amdgcn_raw_buffer_load_b128(rs, j1 * 8, 0, DEC_LAUX);
-        if (need0 && v0[1] == epoch && (j0 + 1 >= n || v0[3] == epoch)) {
-            dst[j0] = __uint_as_float(v0[0]);
-            if (j0 + 1 < n) dst[j0 + 1] = __uint_as_float(v0[2]);
-            need0 = false;
-        }
-        if (need1 && v1[1] == epoch && (j1 + 1 >= n || v1[3] == epoch)) {
-            dst[j1] = __uint_as_float(v1[0]);
-            if (j1 + 1 < n) dst[j1 + 1] = __uint_as_float(v1[2]);
-            need1 = false;
-        }
-        if ((spins & 63) == 63 && (wall_clock64() - t_start > p.timeout_ticks ||
-                                   __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-            ok_all = false;
-            break;
-        }
-        asm volatile("" ::: "memory");
-    }
-    if (!ok_all && (threadIdx.x & 63) == 0) atomicExch(p.status, 1);
-    return __syncthreads_and(ok_all ? 1 : 0) != 0;
-}
-
-// R weight rows (bf16, K % 8 == 0) of one wave: `issue` requests every 16-byte piece (NL per lane and row) -- called BEFORE the
-// wait for the stage's input --, `dot` multiplies them with the fp32 activation vector in LDS.
-template <int R, int NL>
-struct WRows {
-    uint4 w[R][NL];
-    __device__ __forceinline__ void issue(const bf16_t* const (&row)[R], int K, int lane) {
-        const int K8 = K >> 3;
-#pragma unroll
-        for (int j = 0; j < NL; ++j) {
-            const int kk = lane + 64 * j;
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-                w[r][j] = (kk < K8 && row[r]) ? reinterpret_cast<const uint4*>(row[r])[kk] : make_uint4(0u, 0u, 0u, 0u);
-        }
-    }
-    __device__ __forceinline__ void dot(const float* x, int K, int lane, float (&acc)[R]) const {
-        const int K8 = K >> 3;
-        const float4* x4 = reinterpret_cast<const float4*>(x);
-#pragma unroll
-        for (int j = 0; j < NL; ++j) {
-            const int kk = lane + 64 * j;
-            if (kk < K8) {
-                const float4 xa = x4[2 * kk], xb = x4[2 * kk + 1];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    // resident weights (dec_persist_k): an opaque copy keeps the bf16 -> fp32 unpacking INSIDE the frame loop;
-                    // hoisted, the unpacked forms double the live set (480 registers) and spill to scratch
-                    uint4 t = w[r][j];
-                    asm volatile("" : "+v"(t.x), "+v"(t.y), "+v"(t.z), "+v"(t.w));
-                    acc[r] += dot8(t, xa, xb);
-                }
-            }
-        }
-    }
-};
-
-// The same for fp32 weight rows (dec_persist_k<true>: the reference's own inference precision, inference.py:68-71).  A chunk of 8
-// weights is two float4; `issue` requests them, `dot` multiplies.  RESIDENT rows are issued once before the frame loop and live in
-// registers (AGPRs take what the 256 architectural registers cannot hold: the compiler parks them there and reads them back per
-// use); STREAMED rows are re-issued every frame right before the wait for the stage's input and come from the L2 / Infinity Cache.
-template <int R, int NL>
-struct WRowsF {
-    float4 w[R][NL][2];
-    __device__ __forceinline__ void issue(const float* const (&row)[R], int K, int lane) {
-        const int K8 = K >> 3;
-#pragma unroll
-        for (int j = 0; j < NL; ++j) {
-            const int kk = lane + 64 * j;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const bool ok = kk < K8 && row[r];
-                const float4* src = reinterpret_cast<const float4*>(row[r]) + 2 * kk;
-                w[r][j][0] = ok ? src[0] : make_float4(0.f, 0.f, 0.f, 0.f);
-                w[r][j][1] = ok ? src[1] : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        }
-    }
-    __device__ __forceinline__ void dot(const float* x, int K, int lane, float (&acc)[R]) const {
-        const int K8 = K >> 3;
-        const float4* x4 = reinterpret_cast<const float4*>(x);
-#pragma unroll
-        for (int j = 0; j < NL; ++j) {
-            const int kk = lane + 64 * j;
-            if (kk < K8) {
-                const float4 xa = x4[2 * kk], xb = x4[2 * kk + 1];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const float4 a = w[r][j][0], b = w[r][j][1];
-                    acc[r] += (a.x * xa.x + a.y * xa.y + a.z * xa.z + a.w * xa.w) + (b.x * xb.x + b.y * xb.y + b.z * xb.z + b.w * xb.w);
-                }
-            }
-        }
-    }
-};
-
-template <bool PRECISE = false>
-__device__ __forceinline__ void cell_update(const float (&pre)[4], float& c, float& h) {
-    float ig, fg, gg, og, cn;
-    lstm_cell<!PRECISE>(pre, c, ig, fg, gg, og, cn, h);       // fast: v_exp / v_rcp forms (common.h, 16-bit operand modes); precise: libm
-    c = cn;
-}
-// wave sum by DPP butterflies inside the 16-lane rows + four v_readlane (the ds_bpermute ladder of common.h's wave_sum costs
-// ~0.2 us per sum, several sums sit on every stage's critical path); the result is wave-uniform
-__device__ __forceinline__ float wsum(float v) {
-    auto step = [](float x, auto ctrl) {
-        return x + __uint_as_float(__builtin_amdgcn_update_dpp(0u, __float_as_uint(x), decltype(ctrl)::value, 0xf, 0xf, false));
-    };
-    v = step(v, std::integral_constant<int, 0xB1>{});     // quad_perm [1,0,3,2]
-    v = step(v, std::integral_constant<int, 0x4E>{});     // quad_perm [2,3,0,1]
-    v = step(v, std::integral_constant<int, 0x141>{});    // row_half_mirror
-    v = step(v, std::integral_constant<int, 0x140>{});    // row_mirror
-    const unsigned b = __float_as_uint(v);
-    return (__uint_as_float(__builtin_amdgcn_readlane(b, 0)) + __uint_as_float(__builtin_amdgcn_readlane(b, 16))) +
-           (__uint_as_float(__builtin_amdgcn_readlane(b, 32)) + __uint_as_float(__builtin_amdgcn_readlane(b, 48)));
-}
-__device__ __forceinline__ float sfloat(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
-__device__ __forceinline__ float fast_tanh(float x) {
-    return 1.f - 2.f * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(2.f * 1.4426950408889634f * x) + 1.f);
-}
-
-#ifndef FT_DECODE_LIBM
-#define FT_DECODE_LIBM 0
-#endif
-template <int R, int NL, bool F32> using template_rows = typename std::conditional<F32, WRowsF<R, NL>, WRows<R, NL>>::type;
+#include "decode_persist.h"
 
 // F32 = false: 16-bit weight images, all of them register-resident (the round-2 kernel).
 // F32 = true (round 4): fp32 weights and fp32 FMAs -- the operand precision of the reference's inference.py:68-71; activations by the
@@ -1082,6 +857,42 @@ extern "C" size_t ft_decode_wimg_bytes(int H, int A, int M) {
     return tot;
 }
 
+namespace ftdec {
+// the bf16 images of the ten weight matrices into a->wimg; img[k] = the address of image k, in DecodeDev order (decode_dev.h:
+// att_w_ih16 .. conv_w16)
+// (round = false: only the addresses -- an earlier call rounded these weights into a->wimg)
+int make_wimg(const ft_decode_args* a, int n_layers, const unsigned short** img, hipStream_t st, bool round) {
+    FT_CHECK_ARG(a->wimg_bytes >= ft_decode_wimg_bytes(a->H, a->A, a->M) && reinterpret_cast<uintptr_t>(a->wimg) % 256 == 0);
+    FT_CHECK_ARG(a->H % 8 == 0 && a->A % 8 == 0 && a->M % 8 == 0);
+    size_t n[10];
+    wimg_counts(a->H, a->A, a->M, n);
+    // (depth 1: the layer-1 image slots hold copies of layer 0's recurrent matrix -- never read)
+    const float* src[10] = {a->att_w_ih, a->att_w_hh, a->w_query, a->l0_w_ih, a->l0_w_hh, n_layers == 1 ? a->l0_w_hh : a->l1_w_ih,
+                            n_layers == 1 ? a->l0_w_hh : a->l1_w_hh, a->d0_w, a->d1_w, a->conv_w};
+    char* wp = reinterpret_cast<char*>(a->wimg);
+    for (int k = 0; k < 10; ++k) {
+        FT_CHECK_ARG(reinterpret_cast<uintptr_t>(src[k]) % 16 == 0);
+        bf16_t* d = reinterpret_cast<bf16_t*>(wp);
+        if (round) hipLaunchKernelGGL(f32_to_bf16_k, dim3(1024), dim3(256), 0, st, src[k], d, n[k]);
+        img[k] = d;
+        wp += (n[k] * 2 + 255) & ~size_t(255);
+    }
+    return FT_OK;
+}
+
+int device_cus() {
+    static int cus = -1;
+    if (cus < 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 0;
+    }
+    return cus;
+}
+
+long* prof_buf() { return g_decode_prof; }
+}  // namespace ftdec
+
 extern "C" int ft_decode_flow(const ft_decode_args* a, void* stream) {
     FT_CHECK_ARG(a != nullptr);
     FT_CHECK_ARG(a->att_w_ih && a->att_w_hh && a->att_b_ih && a->att_b_hh && a->w_query && a->v && a->K && a->V);
@@ -1106,13 +917,7 @@ extern "C" int ft_decode_flow(const ft_decode_args* a, void* stream) {
     float* fs = reinterpret_cast<float*>(base + lay.off_state);
 
     DecodeDev h{};
-    h.att_w_ih = a->att_w_ih; h.att_w_hh = a->att_w_hh; h.att_b_ih = a->att_b_ih; h.att_b_hh = a->att_b_hh;
-    h.w_query = a->w_query; h.v = a->v; h.K = a->K; h.V = a->V;
-    h.l0_w_ih = a->l0_w_ih; h.l0_w_hh = a->l0_w_hh; h.l0_b_ih = a->l0_b_ih; h.l0_b_hh = a->l0_b_hh;
-    h.l1_w_ih = a->l1_w_ih; h.l1_w_hh = a->l1_w_hh; h.l1_b_ih = a->l1_b_ih; h.l1_b_hh = a->l1_b_hh;
-    h.d0_w = a->d0_w; h.d0_b = a->d0_b; h.d1_w = a->d1_w; h.d1_b = a->d1_b; h.conv_w = a->conv_w; h.conv_b = a->conv_b;
-    h.gate_w = a->gate_w; h.gate_b = a->gate_b;
-    h.residual = a->residual; h.mel_out = a->mel_out; h.attn_out = a->attn_out; h.n_done_dev = a->n_done_dev;
+    fill_dev(a, h);
     h.h_att = fs + lay.h_att; h.c_att = fs + lay.c_att; h.h0 = fs + lay.h0; h.c0 = fs + lay.c0; h.h1 = fs + lay.h1; h.c1 = fs + lay.c1;
     h.q = fs + lay.q; h.ctx = fs + lay.ctx; h.u1 = fs + lay.u1; h.u2 = fs + lay.u2; h.prev = fs + lay.prev;
     h.ctl = reinterpret_cast<int*>(base + lay.off_ctl);
@@ -1122,26 +927,11 @@ extern "C" int ft_decode_flow(const ft_decode_args* a, void* stream) {
         h.cond_w1 = a->cond_w1; h.cond_b1 = a->cond_b1; h.cond_w2 = a->cond_w2; h.cond_b2 = a->cond_b2; h.w_key = a->w_key; h.enc = a->enc;
         h.cumm = fs + lay.cumm; h.prev_attn = fs + lay.prev_attn; h.keyin = fs + lay.keyin; h.Kdyn = fs + lay.Kdyn;
     }
-    h.E = a->E;
-    h.N = a->N; h.L = a->L; h.H = a->H; h.A = a->A; h.M = a->M;
     if (a->wimg) {                               // bf16 weight images: rounded once per call (54 MB of writes vs N x 107 MB of reads)
-        FT_CHECK_ARG(a->wimg_bytes >= ft_decode_wimg_bytes(a->H, a->A, a->M) && reinterpret_cast<uintptr_t>(a->wimg) % 256 == 0);
-        FT_CHECK_ARG(a->H % 8 == 0 && a->A % 8 == 0 && a->M % 8 == 0);
-        size_t n[10];
-        wimg_counts(a->H, a->A, a->M, n);
-        // (depth 1: the layer-1 image slots hold copies of layer 0's recurrent matrix -- never read)
-        const float* src[10] = {a->att_w_ih, a->att_w_hh, a->w_query, a->l0_w_ih, a->l0_w_hh, n_layers == 1 ? a->l0_w_hh : a->l1_w_ih,
-                                n_layers == 1 ? a->l0_w_hh : a->l1_w_hh, a->d0_w, a->d1_w, a->conv_w};
-        const bf16_t** dstp[10] = {&h.att_w_ih16, &h.att_w_hh16, &h.w_query16, &h.l0_w_ih16, &h.l0_w_hh16, &h.l1_w_ih16, &h.l1_w_hh16,
-                                   &h.d0_w16, &h.d1_w16, &h.conv_w16};
-        char* wp = reinterpret_cast<char*>(a->wimg);
-        for (int k = 0; k < 10; ++k) {
-            FT_CHECK_ARG(reinterpret_cast<uintptr_t>(src[k]) % 16 == 0);
-            bf16_t* d = reinterpret_cast<bf16_t*>(wp);
-            hipLaunchKernelGGL(f32_to_bf16_k, dim3(1024), dim3(256), 0, st, src[k], d, n[k]);
-            *dstp[k] = d;
-            wp += (n[k] * 2 + 255) & ~size_t(255);
-        }
+        const unsigned short* img[10];
+        const int rc = ftdec::make_wimg(a, n_layers, img, st, true);
+        if (rc != FT_OK) return rc;
+        set_wimg(h, img);
     }
     h.inv_temp = 1.0f / a->temperature; h.gate_threshold = a->gate_threshold;
 
@@ -1157,13 +947,7 @@ extern "C" int ft_decode_flow(const ft_decode_args* a, void* stream) {
     Depth dep;
     dep.n_layers = n_layers; dep.extra = a->extra_layers; dep.hx = fs + lay.hx; dep.cx = fs + lay.cx;
     if (a->persist_status && n_layers == 2 && !cumm && !a->prior && !a->forced && a->H == 1024 && a->A == 640 && a->M == 80 && a->L <= 1024) {
-        static int cus = -1;
-        if (cus < 0) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 0;
-        }
-        if (cus >= 256) {
+        if (ftdec::device_cus() >= 256) {
             FT_CHECK_ARG(a->persist_gran && reinterpret_cast<uintptr_t>(a->persist_gran) % 16 == 0);
             FT_CHECK_HIP(hipMemsetAsync(a->persist_gran, 0, ft_decode_persist_gran_bytes(), st));   // tags = 0 (epochs start at 1)
             unsigned long long* gr = reinterpret_cast<unsigned long long*>(a->persist_gran);

@@ -225,7 +225,7 @@ class AR_Step(nn.Module):
         """train.py pickles the whole module into its checkpoints (train.py:131-141): the decode scratch (buffers per utterance
         shape, the 54 MB weight image, the hand-off granules) is runtime state, not model state."""
         d = self.__dict__.copy()
-        for k in ("_decode_bufs", "_decode_wimg", "_decode_gran"):
+        for k in ("_decode_bufs", "_decode_wimg", "_decode_gran", "_decode_batch_bufs", "_decode_batch_gran"):
             d.pop(k, None)
         d["_decode_work"] = None
         return d
@@ -458,6 +458,107 @@ class AR_Step(nn.Module):
         attn_rows = [attn_all[i].reshape(1, 1, Lk) for i in range(n)]
         return mel, attn_rows
 
+    def infer_batch(self, x, text, lens):
+        """Sequential inverse of a batch whose utterances have their own lengths: x [T,B,M] (utterance b's frames 0 .. lens[b]-1,
+        zeros behind), text [L,B,E].  Groups of up to ft_decode_batch_max() utterances decode in ONE persistent launch
+        (csrc/decode_batch.hip dec_persist_batch_k), a group of one on ft_decode_flow; every utterance bit for bit as infer() decodes it
+        alone.  Returns (out [T',B,M] zeros behind each utterance's end, attention rows [T',B,1,L], frames per utterance).  The caller
+        has checked the geometry (Flowtron._batch_decode_usable)."""
+        T, B, M = x.shape
+        Lk = text.shape[0]
+        att = self.attention_layer
+        A = att.key.linear_layer.weight.shape[0]
+        H = self.lstm.weight_hh_l0.shape[1]
+        dev = x.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        NB = L.lib().ft_decode_batch_max()
+        has_gate = hasattr(self, "gate_layer")
+        out = torch.zeros(T, B, M, **f32)
+        attn = torch.zeros(T, B, 1, Lk, **f32)
+        n_done_all = torch.zeros(B, device=dev, dtype=torch.int32)
+        lim_host = torch.tensor(lens, dtype=torch.int32).pin_memory()
+        lim_all = lim_host.to(dev, non_blocking=True)
+        if not hasattr(self, "_decode_batch_bufs"):
+            import collections
+            self._decode_batch_bufs = collections.OrderedDict()   # LRU over (nb, N, L, device), as _decode_bufs
+        gran = getattr(self, "_decode_batch_gran", None)
+        if gran is None or gran.device != dev:
+            gran = self._decode_batch_gran = torch.empty(L.lib().ft_decode_batch_gran_bytes(NB), device=dev, dtype=torch.uint8)
+        wimg = None
+        if L.is16(L.mfma_mode()):                                # bf16 weight images, rounded by the flow's first batched launch
+            nbytes = L.lib().ft_decode_wimg_bytes(H, A, M)
+            wimg = getattr(self, "_decode_wimg", None)
+            if wimg is None or wimg.numel() < nbytes or wimg.device != dev:
+                wimg = self._decode_wimg = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        a, p, d = self.attention_lstm, self.lstm, self.dense_layer.layers
+        singles, batched = [], []
+        for g0 in range(0, B, NB):
+            g = list(range(g0, min(g0 + NB, B)))
+            if len(g) == 1:
+                singles.append(g[0])
+                continue
+            batched.append(g)
+            nb, Ng = len(g), max(lens[b] for b in g)
+            key = (nb, Ng, Lk, str(dev))
+            bufs = self._decode_batch_bufs.get(key)
+            if bufs is not None:
+                self._decode_batch_bufs.move_to_end(key)
+            else:
+                while len(self._decode_batch_bufs) >= 8:
+                    self._decode_batch_bufs.popitem(last=False)
+                bufs = self._decode_batch_bufs[key] = dict(
+                    K=torch.empty(nb, Lk, A, **f32), V=torch.empty(nb, Lk, A, **f32), res=torch.empty(nb, Ng, M, **f32),
+                    mel=torch.empty(nb, Ng, M, **f32), attn=torch.empty(nb, Ng, Lk, **f32),
+                    n_done=torch.zeros(nb, device=dev, dtype=torch.int32))
+            K, V, res, mel_out, attn_out, n_done = (bufs[k] for k in ("K", "V", "res", "mel", "attn", "n_done"))
+            for j, b in enumerate(g):
+                tb = text[:, b:b + 1].contiguous()               # the projections of infer(), one utterance at a time
+                K[j].copy_(ops.linear(tb, att.key.linear_layer.weight, None).reshape(Lk, A))
+                V[j].copy_(ops.linear(tb, att.value.linear_layer.weight, None).reshape(Lk, A))
+            res.copy_(x[:Ng, g0:g0 + nb].transpose(0, 1))
+            mel_out.zero_()                                      # rows past an utterance's end are not written
+            attn_out.zero_()
+            n_lim = lim_all[g0:g0 + nb]
+            args = L.DecodeArgs(
+                L.ptr(a.weight_ih_l0), L.ptr(a.weight_hh_l0), L.ptr(a.bias_ih_l0), L.ptr(a.bias_hh_l0),
+                L.ptr(att.query.linear_layer.weight), L.ptr(att.v.linear_layer.weight), L.ptr(K), L.ptr(V),
+                L.ptr(p.weight_ih_l0), L.ptr(p.weight_hh_l0), L.ptr(p.bias_ih_l0), L.ptr(p.bias_hh_l0),
+                L.ptr(p.weight_ih_l1), L.ptr(p.weight_hh_l1), L.ptr(p.bias_ih_l1), L.ptr(p.bias_hh_l1),
+                L.ptr(d[0].linear_layer.weight), L.ptr(d[0].linear_layer.bias),
+                L.ptr(d[1].linear_layer.weight), L.ptr(d[1].linear_layer.bias),
+                L.ptr(self.conv.weight), L.ptr(self.conv.bias),
+                L.ptr(self.gate_layer.linear_layer.weight) if has_gate else None,
+                L.ptr(self.gate_layer.linear_layer.bias) if has_gate else None,
+                L.ptr(res), L.ptr(mel_out), L.ptr(attn_out), L.ptr(n_done), None,
+                0, Ng, Lk, H, A, M, float(att.temperature),
+                float(self.gate_threshold) if has_gate else 2.0, 0,
+                None, None, None, None, None, None, 1, None, None,
+                L.ptr(wimg), wimg.numel() if wimg is not None else 0, L.ptr(gran), L.ptr(ops.persist_status(dev)), 2, None)
+            L.check(L.lib().ft_decode_flow_batch(C.byref(L.DecodeBatchArgs(args, nb, L.ptr(n_lim), int(len(batched) > 1))), L.stream()),
+                    "ft_decode_flow_batch")
+            # copied out on the stream: the next group may reuse these buffers
+            out[:Ng, g0:g0 + nb] = mel_out.transpose(0, 1)
+            attn[:Ng, g0:g0 + nb, 0] = attn_out.transpose(0, 1)
+            n_done_all[g0:g0 + nb] = n_done
+        n = list(lens)
+        if batched:
+            ok = ops.check_persist_status(raise_on_failure=False)
+            if has_gate and ok:
+                n = n_done_all.tolist()                          # the flow's one host read
+            if not ok:
+                # a batched launch did not complete: the device now uses the staged kernels, and these groups decode again one
+                # utterance at a time (infer() keeps its own fallback)
+                singles = sorted(singles + [b for g in batched for b in g])
+        for b in singles:
+            m_, rows = self.infer(x[:lens[b], b:b + 1].contiguous(), text[:, b:b + 1].contiguous())
+            n[b] = m_.shape[0]
+            out[:, b] = 0.0
+            attn[:, b] = 0.0
+            out[:n[b], b] = m_[:, 0]
+            if rows:
+                attn[:n[b], b] = torch.cat(rows, 0)
+        return out, attn, n
+
 
 class AR_Back_Step(nn.Module):
     def __init__(self, n_mel_channels, n_speaker_dim, n_text_dim, n_in_channels, n_hidden, n_attn_channels,
@@ -594,6 +695,8 @@ class Flowtron(nn.Module):
             if attns is not None:
                 raise ValueError("forced alignments (attns=) are taken one utterance at a time")
             sid = speaker_ids.reshape(B, -1)
+            if attn_prior is None and self._batch_decode_usable(residual, text):
+                return self._infer_batched(residual, sid, text, temperature, gate_threshold)
             outs = [self.infer(residual[b:b + 1], sid[b], text[b:b + 1], temperature, gate_threshold, None,
                                None if attn_prior is None else attn_prior[b:b + 1]) for b in range(B)]
             n = max(int(m.shape[2]) for m, _ in outs)
@@ -617,6 +720,50 @@ class Flowtron(nn.Module):
                 x, aw = flow.infer(x, enc, None if attns is None else attns[len(self.flows) - 1 - i], attn_prior=attn_prior)
                 attention_weights.append(aw)
             return x.permute(1, 2, 0), attention_weights
+
+    def _batch_decode_usable(self, residual, text):
+        """True when a batch decodes through the batched persistent launch (AR_Step.infer_batch): its geometry (H 1024, A 640,
+        M 80, L <= 1024, two decoder layers, plain attention) on a device whose persistent kernels work, in either weight precision.  FLOWTRON_DECODE_BATCH=0
+        keeps the utterance-by-utterance loop (the yardstick of the tests); so does FLOWTRON_DECODE_PERSIST=0."""
+        if os.environ.get("FLOWTRON_DECODE_BATCH", "1") == "0" or os.environ.get("FLOWTRON_DECODE_PERSIST", "1") == "0":
+            return False
+        st = self.flows[0].ar_step if hasattr(self.flows[0], "ar_step") else self.flows[0]
+        H = st.lstm.weight_hh_l0.shape[1]
+        A = st.attention_layer.key.linear_layer.weight.shape[0]
+        return (st.n_lstm_layers == 2 and not st.use_cumm_attention and H == 1024 and A == 640 and residual.shape[1] == 80
+                and residual.shape[2] >= 1 and 1 <= text.shape[1] <= 1024 and ops.persist_usable(residual.device))
+
+    def _infer_batched(self, residual, sid, text, temperature, gate_threshold):
+        """infer() of a batch, flow by flow, each flow in groups of up to ft_decode_batch_max() utterances per persistent launch.
+        Every utterance keeps its own length between flows (its own gate stop; the reversed flows flip its own frames), so each
+        comes out exactly as decoded alone; the result has infer()'s batch format."""
+        B = residual.shape[0]
+        with torch.no_grad():
+            # the encoder, utterance by utterance as the loop runs it
+            enc = torch.cat([self._encode(sid[b], text[b:b + 1], None)[0] for b in range(B)], 1)
+            x = residual.permute(2, 0, 1).contiguous().float()
+            lens = [x.shape[0]] * B
+            atts = []
+            for flow in reversed(self.flows):
+                self.set_temperature_and_gate(flow, temperature, gate_threshold)
+                back = hasattr(flow, "ar_step")
+                st = flow.ar_step if back else flow
+                if back:                                         # flowtron.py:631-633 per utterance: flip its own frames
+                    x = ops.reverse_by_length(x, torch.tensor(lens, dtype=torch.int32, device=x.device), True)
+                x, aw, lens = st.infer_batch(x, enc, lens)
+                if back:
+                    x = ops.reverse_by_length(x, torch.tensor(lens, dtype=torch.int32, device=x.device), True)
+                atts.append(aw)
+            n = max(lens)
+            mel = residual.new_zeros(B, x.shape[2], n, dtype=torch.float32)
+            mel.copy_(x[:n].permute(1, 2, 0))
+            rows = []
+            for aw in atts:
+                a_ = residual.new_zeros(n, B, 1, aw.shape[3], dtype=torch.float32)
+                k = min(n, aw.shape[0])
+                a_[:k] = aw[:k]
+                rows.append([a_[t] for t in range(n)])
+            return mel, rows
 
     @staticmethod
     def set_temperature_and_gate(flow, temperature, gate_threshold):

@@ -497,6 +497,26 @@ size_t ft_decode_persist_gran_bytes(void);
 int ft_decode_debug_prof(void* dev_buf);   /* debug: [512][12] int64 stage stamps of the persistent decode, NULL = off */
 int ft_decode_flow(const ft_decode_args* a, void* stream);
 
+/* ---- autoregressive decode of 2 .. ft_decode_batch_max() utterances of one flow in ONE persistent launch ------
+ * Each utterance comes out bit for bit as ft_decode_flow's persistent launch decodes it alone: the hand-offs of a frame carry every
+ * utterance still decoding.  `a` as for ft_decode_flow, with the per-utterance operands nb-strided: K, V [nb][L][A], residual,
+ * mel_out [nb][N][M], attn_out [nb][N][L], n_done_dev [nb]; text is padded to the batch's L.  a.persist_gran (required) holds
+ * ft_decode_batch_gran_bytes(nb) bytes, a.persist_status is required, a.wimg as for ft_decode_flow (NULL = fp32 weights);
+ * wimg_ready != 0: a.wimg already holds the images of these weights (an earlier call of the same flow rounded them).  a.work and
+ * a.use_graph are not used.  n_lim [nb] (device): frames of each utterance (<= N; gate stops end an utterance earlier).  Rows of
+ * mel_out / attn_out past an utterance's end are not written.  FT_EINVAL: nb < 2 or > ft_decode_batch_max(), a NULL or misaligned
+ * pointer (16 bytes; wimg 256).  FT_EUNSUPPORTED: outside the persistent geometry (H 1024, A 640, M 80, L <= 1024, two decoder
+ * layers, no cumulative attention, prior or forced alignment) or not a 256-CU device.  Both before anything reaches the device. */
+typedef struct {
+    ft_decode_args a;
+    int nb;
+    const int32_t* n_lim;
+    int wimg_ready;
+} ft_decode_batch_args;
+int ft_decode_batch_max(void);
+size_t ft_decode_batch_gran_bytes(int nb);
+int ft_decode_flow_batch(const ft_decode_batch_args* a, void* stream);
+
 /* ---- STFT magnitude + mel + log (audio_processing.py:117-134, 207-235) -------
  * y [B,N] in [-1,1] -> mel [B,n_mel,N/hop+1]; window [n_fft] (periodic hann),
  * fb [n_mel, n_fft/2+1].  Radix-2 real FFT per frame in LDS (n_fft = 1024). */

@@ -1,4 +1,5 @@
-// Autoregressive decode of one flow for a batch of utterances in ONE persistent launch (dec_persist_batch_k, ft_decode_flow_batch).
+// Autoregressive decode of one flow for a batch of utterances in ONE persistent launch (dec_persist_batch_k, ft_decode_flow_batch;
+// ft_decode_flow_batch_keys: each utterance with its own text length).
 // Its own translation unit: the kernel shares the hand-off protocol and the dot / cell / softmax helpers of dec_persist_k
 // (decode_persist.h), and compiled into decode.hip's module it changed the register allocation of dec_persist_k<true> (module-level
 // optimisation of the shared helpers); apart, both of decode.hip's persistent kernels keep their instruction streams.
@@ -35,29 +36,35 @@ constexpr int DEC_NBMAX = 4;
 struct DecPB {
     DecP p;                       // p.d: the per-utterance operands are nb-strided (K, V [nb][L][A], residual, mel_out [nb][N][M],
     const int* n_lim;             //   attn_out [nb][N][L], n_done_dev [nb]); n_lim [nb]: frame limit of each utterance (<= N)
+    const int* n_keys;            // [nb] or null: text positions of each utterance (1 ..= L; null = L for all)
     int nb;
 };
 
-// gather() for the live utterances of a batched launch: segment k < nlive is utterance b = byte k of `live`, granules [0, n) at
-// off + b * seg -> dst + b * dst_stride.  The same protocol: 16 lanes of wave 0 per segment relay [relay_lo, n) (n - relay_lo <=
-// 1024), every thread re-reads its granule pairs 2 tid and 2 tid + 512 of every segment while stale.
+// the key count of utterance b: its own text length inside the padded L (read where it is used: a scalar load, no live register)
+__device__ __forceinline__ int keys_of(const int* n_keys, int b, int L) { return n_keys ? min(max(n_keys[b], 1), L) : L; }
+
+// gather() for the live utterances of a batched launch: segment k < nlive is utterance b = byte k of `live`, granules [0, n_b) at
+// off + b * seg -> dst + b * dst_stride, n_b = keys_of(n_keys, b, n) (n_keys null: n for every segment; no one publishes a granule
+// past n_b, so none is waited for).  The same protocol: 16 lanes of wave 0 per segment relay [relay_lo, n_b) (n - relay_lo <= 1024),
+// every thread re-reads its granule pairs 2 tid and 2 tid + 512 of every segment while stale.
 __device__ __forceinline__ bool gather_b(const Relay& R, int off, int seg, int n, int relay_lo, unsigned live, int nlive, unsigned epoch,
-                                         float* dst, int dst_stride, const DecP& p, long t_start) {
+                                         float* dst, int dst_stride, const DecP& p, long t_start, const int* n_keys = nullptr) {
     const int npad = (n + 1) & ~1;
     bool ok_all = true;
     if (relay_lo < n && (int)threadIdx.x < 16 * nlive) {
         const int k = threadIdx.x >> 4, t = threadIdx.x & 15;
-        const int o = off + (int)((live >> (8 * k)) & 255u) * seg;
+        const int b = (int)((live >> (8 * k)) & 255u), nk = keys_of(n_keys, b, n);
+        const int o = off + b * seg;
         const int S = 2 * ((n - relay_lo + 63) >> 6);
         const int j = relay_lo + R.q * S + 2 * t;
-        if (2 * t < S && j < n) {
+        if (2 * t < S && j < nk) {
             __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(R.glob + o, 0, npad * 8, 0x00020000);
             for (unsigned spins = 0;; ++spins) {
                 const du32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rg, j * 8, 0, 16);
-                if (v[1] == epoch && (j + 1 >= n || v[3] == epoch)) {
+                if (v[1] == epoch && (j + 1 >= nk || v[3] == epoch)) {
                     __hip_atomic_store((dgu64*)(R.loc + o + j), ((unsigned long long)v[1] << 32) | v[0], __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_WORKGROUP);
-                    if (j + 1 < n)
+                    if (j + 1 < nk)
                         __hip_atomic_store((dgu64*)(R.loc + o + j + 1), ((unsigned long long)v[3] << 32) | v[2], __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_WORKGROUP);
                     break;
@@ -72,10 +79,15 @@ __device__ __forceinline__ bool gather_b(const Relay& R, int off, int seg, int n
         }
     }
     const int j0 = threadIdx.x * 2, j1 = j0 + 512;
-    unsigned need = 0;                                            // bit 2k: pair j0 of segment k, bit 2k + 1: pair j1
+    // bit 2k: pair j0 of segment k, bit 2k + 1: pair j1; need: the pair starts in the segment, pair: both of its granules are in it
+    unsigned need = 0, pair = 0;
 #pragma unroll
     for (int k = 0; k < DEC_NBMAX; ++k)
-        if (k < nlive) need |= ((j0 < n ? 1u : 0u) | (j1 < n ? 2u : 0u)) << (2 * k);
+        if (k < nlive) {
+            const int nk = keys_of(n_keys, (int)((live >> (8 * k)) & 255u), n);
+            need |= ((j0 < nk ? 1u : 0u) | (j1 < nk ? 2u : 0u)) << (2 * k);
+            pair |= ((j0 + 1 < nk ? 1u : 0u) | (j1 + 1 < nk ? 2u : 0u)) << (2 * k);
+        }
     for (unsigned spins = 0; ok_all && need; ++spins) {
         du32x4 v[DEC_NBMAX][2];
 #pragma unroll
@@ -87,14 +99,14 @@ __device__ __forceinline__ bool gather_b(const Relay& R, int off, int seg, int n
 #pragma unroll
         for (int k = 0; k < DEC_NBMAX; ++k) {
             float* const d = dst + (int)((live >> (8 * k)) & 255u) * dst_stride;
-            if ((need & (1u << (2 * k))) && v[k][0][1] == epoch && (j0 + 1 >= n || v[k][0][3] == epoch)) {
+            if ((need & (1u << (2 * k))) && v[k][0][1] == epoch && (!(pair & (1u << (2 * k))) || v[k][0][3] == epoch)) {
                 d[j0] = __uint_as_float(v[k][0][0]);
-                if (j0 + 1 < n) d[j0 + 1] = __uint_as_float(v[k][0][2]);
+                if (pair & (1u << (2 * k))) d[j0 + 1] = __uint_as_float(v[k][0][2]);
                 need &= ~(1u << (2 * k));
             }
-            if ((need & (2u << (2 * k))) && v[k][1][1] == epoch && (j1 + 1 >= n || v[k][1][3] == epoch)) {
+            if ((need & (2u << (2 * k))) && v[k][1][1] == epoch && (!(pair & (2u << (2 * k))) || v[k][1][3] == epoch)) {
                 d[j1] = __uint_as_float(v[k][1][0]);
-                if (j1 + 1 < n) d[j1 + 1] = __uint_as_float(v[k][1][2]);
+                if (pair & (2u << (2 * k))) d[j1 + 1] = __uint_as_float(v[k][1][2]);
                 need &= ~(2u << (2 * k));
             }
         }
@@ -283,11 +295,11 @@ __global__ __launch_bounds__(256, 1) void dec_persist_batch_k(const DecPB pb) {
                 if (lane == 0) publish_local(R.loc + gQ + b * A + slot + 128 * r, e0 + 2u, v);
             }
         }
-        // ================= S3a: scores of text positions slot + 128 k (key rows from the L2)
+        // ================= S3a: scores of text positions slot + 128 k < L_b (key rows from the L2)
         if (!gather_b(R, gQ, A, A, A, live, nlive, e0 + 2u, &s_q[0][0], A, p, t_start)) return;
         stamp(4);
         for (int k = 0; k < nlive; ++k) {
-            const int b = lv(k);
+            const int b = lv(k), Lb = keys_of(pb.n_keys, b, L);  // (utterance b's own text: dec_persist_k's code at L = Lb)
             const float* const Kb = P.K + (size_t)b * L * A;
             // dec_persist_k's shape of this stage: the first KRES positions from registers, unrolled, the rest in the loop (the same
             // expressions; the compiler fuses the two shapes differently, so the shape is kept); here the registers are filled from
@@ -296,17 +308,17 @@ __global__ __launch_bounds__(256, 1) void dec_persist_batch_k(const DecPB pb) {
 #pragma unroll
             for (int j = 0; j < A / 64; ++j)
 #pragma unroll
-                for (int kk = 0; kk < KRES; ++kk) k_row[kk][j] = slot + 128 * kk < L ? Kb[(size_t)(slot + 128 * kk) * A + lane + 64 * j] : 0.f;
+                for (int kk = 0; kk < KRES; ++kk) k_row[kk][j] = slot + 128 * kk < Lb ? Kb[(size_t)(slot + 128 * kk) * A + lane + 64 * j] : 0.f;
 #pragma unroll
             for (int kk = 0; kk < KRES; ++kk)
-                if (slot + 128 * kk < L) {
+                if (slot + 128 * kk < Lb) {
                     float sc = 0.f;
 #pragma unroll
                     for (int j = 0; j < A / 64; ++j) sc += s_v[lane + 64 * j] * act_tanh(s_q[b][lane + 64 * j] + k_row[kk][j]);
                     sc = wsum(sc);
                     if (lane == 0) publish_local(R.loc + gSC + b * LMAX + slot + 128 * kk, e0 + 3u, sc * P.inv_temp);
                 }
-            for (int l = slot + 128 * KRES; l < L; l += 128) {
+            for (int l = slot + 128 * KRES; l < Lb; l += 128) {
                 float sc = 0.f;
 #pragma unroll
                 for (int j = 0; j < A / 64; ++j) sc += s_v[lane + 64 * j] * act_tanh(s_q[b][lane + 64 * j] + Kb[(size_t)l * A + lane + 64 * j]);
@@ -314,31 +326,31 @@ __global__ __launch_bounds__(256, 1) void dec_persist_batch_k(const DecPB pb) {
                 if (lane == 0) publish_local(R.loc + gSC + b * LMAX + l, e0 + 3u, sc * P.inv_temp);
             }
         }
-        // ================= S3b: softmax over L, context channels slot + 128 k (value columns from the L2)
-        if (!gather_b(R, gSC, LMAX, L, L, live, nlive, e0 + 3u, &s_pr[0][0], LMAX, p, t_start)) return;
+        // ================= S3b: softmax over L_b, context channels slot + 128 k (value columns from the L2; attn_out rows of stride L)
+        if (!gather_b(R, gSC, LMAX, L, L, live, nlive, e0 + 3u, &s_pr[0][0], LMAX, p, t_start, pb.n_keys)) return;
         stamp(5);
         for (int k = 0; k < nlive; ++k) {
-            const int b = lv(k);
+            const int b = lv(k), Lb = keys_of(pb.n_keys, b, L);
             float* const pr = s_pr[b];
             const float* const Vb = P.V + (size_t)b * L * A;
             float v_col[5][VRES];                                 // (requested before the softmax; dec_persist_k's shape, as the scores)
 #pragma unroll
             for (int r = 0; r < 5; ++r)
 #pragma unroll
-                for (int j = 0; j < VRES; ++j) v_col[r][j] = lane + 64 * j < L ? Vb[(size_t)(lane + 64 * j) * A + slot + 128 * r] : 0.f;
+                for (int j = 0; j < VRES; ++j) v_col[r][j] = lane + 64 * j < Lb ? Vb[(size_t)(lane + 64 * j) * A + slot + 128 * r] : 0.f;
             float m = -INFINITY;
-            for (int l = tid; l < L; l += 256) m = fmaxf(m, pr[l]);
+            for (int l = tid; l < Lb; l += 256) m = fmaxf(m, pr[l]);
             m = wave_max(m);
             if (lane == 0) s_red[wave] = m;
             __syncthreads();
             m = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
             float sum = 0.f;
-            for (int l = tid; l < L; l += 256) { const float e = expf(pr[l] - m); pr[l] = e; sum += e; }
+            for (int l = tid; l < Lb; l += 256) { const float e = expf(pr[l] - m); pr[l] = e; sum += e; }
             sum = wsum(sum);
             if (lane == 0) s_red[4 + wave] = sum;
             __syncthreads();
             sum = s_red[4] + s_red[5] + s_red[6] + s_red[7];
-            for (int l = tid; l < L; l += 256) {
+            for (int l = tid; l < Lb; l += 256) {
                 const float pl = pr[l] / sum;
                 pr[l] = pl;
                 if (c == 0) P.attn_out[((size_t)b * N + i) * L + l] = pl;
@@ -346,13 +358,13 @@ __global__ __launch_bounds__(256, 1) void dec_persist_batch_k(const DecPB pb) {
             __syncthreads();
             float pl[VRES];
 #pragma unroll
-            for (int j = 0; j < VRES; ++j) pl[j] = lane + 64 * j < L ? pr[lane + 64 * j] : 0.f;
+            for (int j = 0; j < VRES; ++j) pl[j] = lane + 64 * j < Lb ? pr[lane + 64 * j] : 0.f;
 #pragma unroll
             for (int r = 0; r < 5; ++r) {
                 float cx = 0.f;
 #pragma unroll
                 for (int j = 0; j < VRES; ++j) cx += pl[j] * v_col[r][j];
-                for (int l = lane + 64 * VRES; l < L; l += 64) cx += pr[l] * Vb[(size_t)l * A + slot + 128 * r];
+                for (int l = lane + 64 * VRES; l < Lb; l += 64) cx += pr[l] * Vb[(size_t)l * A + slot + 128 * r];
                 cx = wsum(cx);
                 if (lane == 0) publish_local(R.loc + gCTX + b * A + slot + 128 * r, e0 + 4u, cx);
             }
@@ -453,7 +465,7 @@ extern "C" int ft_decode_batch_max(void) { return DEC_NBMAX; }
 // the producers' copy + one copy per XCD, each nb times the single-utterance layout, + the census counters
 extern "C" size_t ft_decode_batch_gran_bytes(int nb) { return nb < 1 ? 0 : (size_t)G_TOTAL * nb * 8 * 9 + 64; }
 
-extern "C" int ft_decode_flow_batch(const ft_decode_batch_args* ba, void* stream) {
+extern "C" int ft_decode_flow_batch_keys(const ft_decode_batch_args* ba, const int32_t* n_keys, void* stream) {
     FT_CHECK_ARG(ba != nullptr);
     const ft_decode_args* a = &ba->a;
     const int nb = ba->nb;
@@ -467,6 +479,7 @@ extern "C" int ft_decode_flow_batch(const ft_decode_batch_args* ba, void* stream
     const void* al16[] = {a->att_w_ih, a->att_w_hh, a->w_query, a->K, a->V, a->l0_w_ih, a->l0_w_hh, a->l1_w_ih, a->l1_w_hh,
                           a->d0_w, a->d1_w, a->conv_w, a->residual, a->mel_out, a->attn_out, a->persist_gran};
     for (const void* q : al16) FT_CHECK_ARG(reinterpret_cast<uintptr_t>(q) % 16 == 0);
+    FT_CHECK_ARG(reinterpret_cast<uintptr_t>(n_keys) % 4 == 0);
     FT_CHECK_ARG(!a->wimg || (a->wimg_bytes >= ft_decode_wimg_bytes(a->H, a->A, a->M) && reinterpret_cast<uintptr_t>(a->wimg) % 256 == 0));
     const int n_layers = a->n_layers > 0 ? a->n_layers : 2;
     if (n_layers != 2 || a->cond_w1 || a->prior || a->forced || a->H != 1024 || a->A != 640 || a->M != 80 || a->L > 1024)
@@ -488,9 +501,11 @@ extern "C" int ft_decode_flow_batch(const ft_decode_batch_args* ba, void* stream
     FT_CHECK_HIP(hipMemsetAsync(a->n_done_dev, 0, sizeof(int) * nb, st));
     unsigned long long* gr = reinterpret_cast<unsigned long long*>(a->persist_gran);
     DecPB pb{DecP{h, gr, reinterpret_cast<unsigned*>(gr + (size_t)G_TOTAL * nb * 9), a->persist_status, 100000000L / 2, ftdec::prof_buf()},
-             ba->n_lim, nb};
+             ba->n_lim, n_keys, nb};
     if (a->wimg) hipLaunchKernelGGL(dec_persist_batch_k<false>, dim3(256), dim3(256), 0, st, pb);
     else hipLaunchKernelGGL(dec_persist_batch_k<true>, dim3(256), dim3(256), 0, st, pb);
     FT_CHECK_LAUNCH();
     return FT_OK;
 }
+
+extern "C" int ft_decode_flow_batch(const ft_decode_batch_args* ba, void* stream) { return ft_decode_flow_batch_keys(ba, nullptr, stream); }

@@ -10,6 +10,7 @@ CPU tensors raises (the CPU oracle is oracle/flowtron_oracle.py, test infrastruc
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 import os
 from typing import List, Optional
 
@@ -458,14 +459,17 @@ class AR_Step(nn.Module):
         attn_rows = [attn_all[i].reshape(1, 1, Lk) for i in range(n)]
         return mel, attn_rows
 
-    def infer_batch(self, x, text, lens):
-        """Sequential inverse of a batch whose utterances have their own lengths: x [T,B,M] (utterance b's frames 0 .. lens[b]-1,
-        zeros behind), text [L,B,E].  Groups of up to ft_decode_batch_max() utterances decode in ONE persistent launch
-        (csrc/decode_batch.hip dec_persist_batch_k), a group of one on ft_decode_flow; every utterance bit for bit as infer() decodes it
-        alone.  Returns (out [T',B,M] zeros behind each utterance's end, attention rows [T',B,1,L], frames per utterance).  The caller
-        has checked the geometry (Flowtron._batch_decode_usable)."""
+    def infer_batch(self, x, text, lens, in_lens=None):
+        """Sequential inverse of a batch whose utterances have their own lengths: x [T,B,M] (utterance b's frames 0 .. lens[b]-1;
+        the frames behind are not read), text [L,B,E] (utterance b's positions 0 .. in_lens[b]-1, None = all L; the positions behind
+        are not read).  Groups of up to ft_decode_batch_max() utterances decode in ONE persistent launch (csrc/decode_batch.hip
+        dec_persist_batch_k; ft_decode_flow_batch_keys where a group's texts differ in length), a group of one on ft_decode_flow;
+        every utterance bit for bit as infer() decodes it alone.  Returns (out [T',B,M] zeros behind each utterance's end, attention
+        rows [T',B,1,L] zeros behind its end and its text, frames per utterance).  The caller has checked the geometry
+        (Flowtron._batch_decode_usable)."""
         T, B, M = x.shape
         Lk = text.shape[0]
+        il = list(in_lens) if in_lens is not None else [Lk] * B
         att = self.attention_layer
         A = att.key.linear_layer.weight.shape[0]
         H = self.lstm.weight_hh_l0.shape[1]
@@ -478,6 +482,7 @@ class AR_Step(nn.Module):
         n_done_all = torch.zeros(B, device=dev, dtype=torch.int32)
         lim_host = torch.tensor(lens, dtype=torch.int32).pin_memory()
         lim_all = lim_host.to(dev, non_blocking=True)
+        keys_all = torch.tensor(il, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
         if not hasattr(self, "_decode_batch_bufs"):
             import collections
             self._decode_batch_bufs = collections.OrderedDict()   # LRU over (nb, N, L, device), as _decode_bufs
@@ -512,9 +517,10 @@ class AR_Step(nn.Module):
                     n_done=torch.zeros(nb, device=dev, dtype=torch.int32))
             K, V, res, mel_out, attn_out, n_done = (bufs[k] for k in ("K", "V", "res", "mel", "attn", "n_done"))
             for j, b in enumerate(g):
-                tb = text[:, b:b + 1].contiguous()               # the projections of infer(), one utterance at a time
-                K[j].copy_(ops.linear(tb, att.key.linear_layer.weight, None).reshape(Lk, A))
-                V[j].copy_(ops.linear(tb, att.value.linear_layer.weight, None).reshape(Lk, A))
+                # the projections of infer(), one utterance at a time over its own positions (rows behind them are not read)
+                tb = text[:il[b], b:b + 1].contiguous()
+                K[j, :il[b]].copy_(ops.linear(tb, att.key.linear_layer.weight, None).reshape(il[b], A))
+                V[j, :il[b]].copy_(ops.linear(tb, att.value.linear_layer.weight, None).reshape(il[b], A))
             res.copy_(x[:Ng, g0:g0 + nb].transpose(0, 1))
             mel_out.zero_()                                      # rows past an utterance's end are not written
             attn_out.zero_()
@@ -534,8 +540,12 @@ class AR_Step(nn.Module):
                 float(self.gate_threshold) if has_gate else 2.0, 0,
                 None, None, None, None, None, None, 1, None, None,
                 L.ptr(wimg), wimg.numel() if wimg is not None else 0, L.ptr(gran), L.ptr(ops.persist_status(dev)), 2, None)
-            L.check(L.lib().ft_decode_flow_batch(C.byref(L.DecodeBatchArgs(args, nb, L.ptr(n_lim), int(len(batched) > 1))), L.stream()),
-                    "ft_decode_flow_batch")
+            bargs = L.DecodeBatchArgs(args, nb, L.ptr(n_lim), int(len(batched) > 1))
+            if any(il[b] < Lk for b in g):                       # texts of different lengths: a key count per utterance
+                L.check(L.lib().ft_decode_flow_batch_keys(C.byref(bargs), L.ptr(keys_all[g0:g0 + nb]), L.stream()),
+                        "ft_decode_flow_batch_keys")
+            else:
+                L.check(L.lib().ft_decode_flow_batch(C.byref(bargs), L.stream()), "ft_decode_flow_batch")
             # copied out on the stream: the next group may reuse these buffers
             out[:Ng, g0:g0 + nb] = mel_out.transpose(0, 1)
             attn[:Ng, g0:g0 + nb, 0] = attn_out.transpose(0, 1)
@@ -550,13 +560,13 @@ class AR_Step(nn.Module):
                 # utterance at a time (infer() keeps its own fallback)
                 singles = sorted(singles + [b for g in batched for b in g])
         for b in singles:
-            m_, rows = self.infer(x[:lens[b], b:b + 1].contiguous(), text[:, b:b + 1].contiguous())
+            m_, rows = self.infer(x[:lens[b], b:b + 1].contiguous(), text[:il[b], b:b + 1].contiguous())
             n[b] = m_.shape[0]
             out[:, b] = 0.0
             attn[:, b] = 0.0
             out[:n[b], b] = m_[:, 0]
             if rows:
-                attn[:n[b], b] = torch.cat(rows, 0)
+                attn[:n[b], b, :, :il[b]] = torch.cat(rows, 0)
         return out, attn, n
 
 
@@ -582,6 +592,30 @@ class AR_Back_Step(nn.Module):
             attn_prior = torch.flip(attn_prior, (1,))                     # flowtron.py:631-633 (batch 1: flip only)
         out, attn = self.ar_step.infer(torch.flip(residual, (0,)), text, attns, attn_prior=attn_prior)
         return torch.flip(out, (0,)), attn
+
+
+def lengths_arg(v, name, B, hi):
+    """in_lens / out_lens of Flowtron.infer -> a list of B Python ints in 1 ..= hi (None -> None).  A list or tuple of integers,
+    or a one-dimensional integer tensor on the host or the device (read to the host once).  ValueError otherwise."""
+    if v is None:
+        return None
+    if torch.is_tensor(v):
+        if v.dtype.is_floating_point or v.dtype.is_complex or v.dtype == torch.bool:
+            raise ValueError("%s must hold integers, got a %s tensor" % (name, v.dtype))
+        if v.dim() != 1:
+            raise ValueError("%s must be one-dimensional [B], got shape %s" % (name, tuple(v.shape)))
+        vals = v.tolist()
+    else:
+        if not isinstance(v, (list, tuple)):
+            raise ValueError("%s must be a list, tuple or tensor of integers, got %s" % (name, type(v).__name__))
+        if any(isinstance(x, bool) or not isinstance(x, numbers.Integral) for x in v):
+            raise ValueError("%s must hold integers, got %r" % (name, list(v)))
+        vals = [int(x) for x in v]
+    if len(vals) != B:
+        raise ValueError("%s has %d entries for a batch of %d" % (name, len(vals), B))
+    if any(not 1 <= x <= hi for x in vals):
+        raise ValueError("%s must lie in 1 ..= %d, got %r" % (name, hi, vals))
+    return vals
 
 
 # --------------------------------------------------------------------------
@@ -682,33 +716,62 @@ class Flowtron(nn.Module):
                 x, log_s_list, gate, attns_list, attns_logprob_list = run_flows(x0, enc)
         return x, log_s_list, gate, attns_list, attns_logprob_list, None, None, None
 
-    def infer(self, residual, speaker_ids, text, temperature=1.0, gate_threshold=0.5, attns=None, attn_prior=None):
+    def infer(self, residual, speaker_ids, text, temperature=1.0, gate_threshold=0.5, attns=None, attn_prior=None,
+              in_lens=None, out_lens=None, return_lengths=False):
         """residual [B,M,N], speaker_ids [B] or [B,1], text [B,L] -> (mel [B,M,N'], attention_weights: per flow a list of N' rows
         [B,1,L]).  The decode kernels are batch-1 chains (inference.py decodes one utterance).  A batch (the reference's loop takes any,
         flowtron.py:775-828, 901-930) is decoded utterance by utterance through ALL flows and padded only at the very end: with a gate
         layer every utterance stops at its OWN frame of the last flow (decoded first), and the flows behind it must see exactly that
         utterance's frames -- padding the batch after each flow would put the shorter utterances' pad frames IN FRONT of their real
-        ones once the next (reversed) flow flips the tensor.  Frames behind an utterance's stop are zero; N' = the longest."""
+        ones once the next (reversed) flow flips the tensor.  Frames behind an utterance's stop are zero; N' = the longest.
+
+        Sentences of different lengths (this project's extension; the reference's infer is batch-1): in_lens [B] text positions and
+        out_lens [B] residual frames per utterance (lists, CPU or device integer tensors; 1 ..= L and 1 ..= N; None = all of them).
+        Utterance b is decoded exactly as infer(residual[b:b+1, :, :out_lens[b]], speaker_ids[b:b+1], text[b:b+1, :in_lens[b]]):
+        token ids and residual frames behind its lengths are never read, and its attention columns >= in_lens[b] are zero.
+        attn_prior [B,N,L] is cut the same way.  return_lengths=True appends a CPU int64 [B]: the frames each utterance produced
+        (out_lens[b], fewer where the gate stopped it)."""
         L.require_cuda(residual, text)
         B = residual.shape[0]
-        if B > 1:
-            if attns is not None:
-                raise ValueError("forced alignments (attns=) are taken one utterance at a time")
+        if residual.dim() != 3 or text.dim() != 2 or text.shape[0] != B:
+            raise ValueError("residual must be [B, M, N] and text [B, L] with the same B, got %s and %s"
+                             % (tuple(residual.shape), tuple(text.shape)))
+        Lt, N = text.shape[1], residual.shape[2]
+        il = lengths_arg(in_lens, "in_lens", B, Lt) or [Lt] * B
+        ol = lengths_arg(out_lens, "out_lens", B, N) or [N] * B
+        if B > 1 and attns is not None:
+            raise ValueError("forced alignments (attns=) are taken one utterance at a time")
+        if B == 1:
+            if attns is not None and (il[0] < Lt or ol[0] < N):   # one forced alignment per flow: N rows of L
+                attns = [(torch.stack([r.reshape(-1) for r in a]) if isinstance(a, (list, tuple)) else a.reshape(-1, Lt))[:ol[0], :il[0]]
+                         for a in attns]
+            mel, aws = self._infer_one(residual[:, :, :ol[0]], speaker_ids, text[:, :il[0]], temperature, gate_threshold, attns,
+                                       None if attn_prior is None else attn_prior[:, :ol[0], :il[0]])
+            if il[0] < Lt:                                       # the rows at the width of the given text, zeros behind in_lens
+                aws = [[torch.nn.functional.pad(r, (0, Lt - il[0])) for r in rows] for rows in aws]
+            n = [int(mel.shape[2])]
+        else:
             sid = speaker_ids.reshape(B, -1)
-            if attn_prior is None and self._batch_decode_usable(residual, text):
-                return self._infer_batched(residual, sid, text, temperature, gate_threshold)
-            outs = [self.infer(residual[b:b + 1], sid[b], text[b:b + 1], temperature, gate_threshold, None,
-                               None if attn_prior is None else attn_prior[b:b + 1]) for b in range(B)]
-            n = max(int(m.shape[2]) for m, _ in outs)
-            mel = residual.new_zeros(B, outs[0][0].shape[1], n, dtype=torch.float32)
-            Lk = text.shape[1]
-            atts = [residual.new_zeros(n, B, 1, Lk, dtype=torch.float32) for _ in self.flows]
-            for b, (m, aws) in enumerate(outs):
-                mel[b, :, :m.shape[2]] = m[0]
-                for f, rows in enumerate(aws):
-                    if rows:
-                        atts[f][:len(rows), b] = torch.stack([r.reshape(1, Lk) for r in rows])
-            return mel, [[a[t] for t in range(n)] for a in atts]
+            if attn_prior is None and self._batch_decode_usable(residual, max(il)):
+                mel, aws, n = self._infer_batched(residual, sid, text, temperature, gate_threshold, il, ol)
+            else:
+                outs = [self._infer_one(residual[b:b + 1, :, :ol[b]], sid[b], text[b:b + 1, :il[b]], temperature, gate_threshold,
+                                        None, None if attn_prior is None else attn_prior[b:b + 1, :ol[b], :il[b]]) for b in range(B)]
+                n = [int(m.shape[2]) for m, _ in outs]
+                mel = residual.new_zeros(B, outs[0][0].shape[1], max(n), dtype=torch.float32)
+                atts = [residual.new_zeros(max(n), B, 1, Lt, dtype=torch.float32) for _ in self.flows]
+                for b, (m, aw) in enumerate(outs):
+                    mel[b, :, :m.shape[2]] = m[0]
+                    for f, rows in enumerate(aw):
+                        if rows:
+                            atts[f][:len(rows), b, :, :il[b]] = torch.stack([r.reshape(1, il[b]) for r in rows])
+                aws = [[a[t] for t in range(max(n))] for a in atts]
+        if return_lengths:
+            return mel, aws, torch.tensor(n, dtype=torch.int64)
+        return mel, aws
+
+    def _infer_one(self, residual, speaker_ids, text, temperature, gate_threshold, attns, attn_prior):
+        """infer() of one utterance: residual [1,M,N], text [1,L], every position and frame its own"""
         with torch.no_grad():
             enc, _ = self._encode(speaker_ids, text, None)
             x = residual.permute(2, 0, 1).contiguous().float()
@@ -721,28 +784,36 @@ class Flowtron(nn.Module):
                 attention_weights.append(aw)
             return x.permute(1, 2, 0), attention_weights
 
-    def _batch_decode_usable(self, residual, text):
+    def _batch_decode_usable(self, residual, n_text):
         """True when a batch decodes through the batched persistent launch (AR_Step.infer_batch): its geometry (H 1024, A 640,
-        M 80, L <= 1024, two decoder layers, plain attention) on a device whose persistent kernels work, in either weight precision.  FLOWTRON_DECODE_BATCH=0
-        keeps the utterance-by-utterance loop (the yardstick of the tests); so does FLOWTRON_DECODE_PERSIST=0."""
+        M 80, longest text n_text <= 1024, two decoder layers, plain attention) on a device whose persistent kernels work, in either
+        weight precision.  FLOWTRON_DECODE_BATCH=0 keeps the utterance-by-utterance loop (the yardstick of the tests); so does
+        FLOWTRON_DECODE_PERSIST=0."""
         if os.environ.get("FLOWTRON_DECODE_BATCH", "1") == "0" or os.environ.get("FLOWTRON_DECODE_PERSIST", "1") == "0":
             return False
         st = self.flows[0].ar_step if hasattr(self.flows[0], "ar_step") else self.flows[0]
         H = st.lstm.weight_hh_l0.shape[1]
         A = st.attention_layer.key.linear_layer.weight.shape[0]
         return (st.n_lstm_layers == 2 and not st.use_cumm_attention and H == 1024 and A == 640 and residual.shape[1] == 80
-                and residual.shape[2] >= 1 and 1 <= text.shape[1] <= 1024 and ops.persist_usable(residual.device))
+                and residual.shape[2] >= 1 and 1 <= n_text <= 1024 and ops.persist_usable(residual.device))
 
-    def _infer_batched(self, residual, sid, text, temperature, gate_threshold):
+    def _infer_batched(self, residual, sid, text, temperature, gate_threshold, in_lens, out_lens):
         """infer() of a batch, flow by flow, each flow in groups of up to ft_decode_batch_max() utterances per persistent launch.
-        Every utterance keeps its own length between flows (its own gate stop; the reversed flows flip its own frames), so each
-        comes out exactly as decoded alone; the result has infer()'s batch format."""
-        B = residual.shape[0]
+        Every utterance keeps its own text (in_lens: its own encoder call, keys and values) and its own length between flows
+        (out_lens, then its own gate stop; the reversed flows flip its own frames), so each comes out exactly as decoded alone.
+        Returns infer()'s batch format and the frames of each utterance."""
+        B, Lt = residual.shape[0], text.shape[1]
+        Lk = max(in_lens)                                        # the text, padded to its longest utterance only
         with torch.no_grad():
-            # the encoder, utterance by utterance as the loop runs it
-            enc = torch.cat([self._encode(sid[b], text[b:b + 1], None)[0] for b in range(B)], 1)
-            x = residual.permute(2, 0, 1).contiguous().float()
-            lens = [x.shape[0]] * B
+            # the encoder, utterance by utterance as the loop runs it, each over its own positions; zeros behind them
+            enc = None
+            for b in range(B):
+                e = self._encode(sid[b], text[b:b + 1, :in_lens[b]], None)[0]
+                if enc is None:
+                    enc = e.new_zeros(Lk, B, e.shape[2])
+                enc[:in_lens[b], b] = e[:, 0]
+            x = residual[:, :, :max(out_lens)].permute(2, 0, 1).contiguous().float()    # (frames past out_lens[b] are never read)
+            lens = list(out_lens)
             atts = []
             for flow in reversed(self.flows):
                 self.set_temperature_and_gate(flow, temperature, gate_threshold)
@@ -750,7 +821,7 @@ class Flowtron(nn.Module):
                 st = flow.ar_step if back else flow
                 if back:                                         # flowtron.py:631-633 per utterance: flip its own frames
                     x = ops.reverse_by_length(x, torch.tensor(lens, dtype=torch.int32, device=x.device), True)
-                x, aw, lens = st.infer_batch(x, enc, lens)
+                x, aw, lens = st.infer_batch(x, enc, lens, in_lens)
                 if back:
                     x = ops.reverse_by_length(x, torch.tensor(lens, dtype=torch.int32, device=x.device), True)
                 atts.append(aw)
@@ -759,11 +830,11 @@ class Flowtron(nn.Module):
             mel.copy_(x[:n].permute(1, 2, 0))
             rows = []
             for aw in atts:
-                a_ = residual.new_zeros(n, B, 1, aw.shape[3], dtype=torch.float32)
+                a_ = residual.new_zeros(n, B, 1, Lt, dtype=torch.float32)
                 k = min(n, aw.shape[0])
-                a_[:k] = aw[:k]
+                a_[:k, :, :, :Lk] = aw[:k]
                 rows.append([a_[t] for t in range(n)])
-            return mel, rows
+            return mel, rows, lens
 
     @staticmethod
     def set_temperature_and_gate(flow, temperature, gate_threshold):

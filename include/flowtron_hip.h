@@ -506,7 +506,11 @@ int ft_decode_flow(const ft_decode_args* a, void* stream);
  * a.use_graph are not used.  n_lim [nb] (device): frames of each utterance (<= N; gate stops end an utterance earlier).  Rows of
  * mel_out / attn_out past an utterance's end are not written.  FT_EINVAL: nb < 2 or > ft_decode_batch_max(), a NULL or misaligned
  * pointer (16 bytes; wimg 256).  FT_EUNSUPPORTED: outside the persistent geometry (H 1024, A 640, M 80, L <= 1024, two decoder
- * layers, no cumulative attention, prior or forced alignment) or not a 256-CU device.  Both before anything reaches the device. */
+ * layers, no cumulative attention, prior or forced alignment) or not a 256-CU device.  Both before anything reaches the device.
+ * ft_decode_flow_batch_keys: the same with a text length per utterance.  n_keys [nb] (device int32, each 1 ..= a.L; 4-byte
+ * aligned): utterance b attends to key / value rows 0 .. n_keys[b]-1 of its K, V only, exactly as ft_decode_flow decodes it alone
+ * at L = n_keys[b]; its attn_out columns >= n_keys[b] are not written (row stride stays a.L).  NULL = a.L for every utterance,
+ * which is ft_decode_flow_batch. */
 typedef struct {
     ft_decode_args a;
     int nb;
@@ -516,6 +520,7 @@ typedef struct {
 int ft_decode_batch_max(void);
 size_t ft_decode_batch_gran_bytes(int nb);
 int ft_decode_flow_batch(const ft_decode_batch_args* a, void* stream);
+int ft_decode_flow_batch_keys(const ft_decode_batch_args* a, const int32_t* n_keys, void* stream);
 
 /* ---- STFT magnitude + mel + log (audio_processing.py:117-134, 207-235) -------
  * y [B,N] in [-1,1] -> mel [B,n_mel,N/hop+1]; window [n_fft] (periodic hann),

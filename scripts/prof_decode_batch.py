@@ -2,9 +2,12 @@
 ft_decode_batch_max() utterances) against the utterance-by-utterance loop (FLOWTRON_DECODE_BATCH=0), alternating in one process.
 Full-width synthetic 2-flow model, L 150, N 400, ungated, B = 1, 2, 4, 8, fp32 weights and bf16 weight images: device-event time of whole
 warm infer calls, median and spread; us per frame and flow, utterance-frames/s.  --stages: per-stage times inside the launch at B = 1 and 4 from the ft_decode_debug_prof stamps of workgroup 0 (the last flow's launch;
-medians over the frames).  Kernel times: a separate
+medians over the frames).  --text-lens 40,80,150,300: sentences of different lengths instead, B = their number, three ways
+alternating: (a) the ragged batch (in_lens: a key count per utterance), (b) the loop over the trimmed utterances
+(FLOWTRON_DECODE_BATCH=0, same in_lens), (c) the same batch unragged at L = the longest (no in_lens).  Kernel times: a separate
 `rocprofv3 --kernel-trace --stats -- python scripts/prof_decode_batch.py --reps 1 --warmup 1` run.
-usage: python scripts/prof_decode_batch.py [--reps R] [--warmup W] [--modes f32,bf16] [--stages] [--batches 1,2,4,8]"""
+usage: python scripts/prof_decode_batch.py [--reps R] [--warmup W] [--modes f32,bf16] [--stages] [--batches 1,2,4,8]
+                                           [--text-lens 40,80,150,300]"""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -20,7 +23,11 @@ ap.add_argument("--text", type=int, default=150)
 ap.add_argument("--modes", default="f32,bf16")
 ap.add_argument("--batches", default="1,2,4,8")
 ap.add_argument("--stages", action="store_true")
+ap.add_argument("--text-lens", default="")
 a = ap.parse_args()
+text_lens = [int(x) for x in a.text_lens.split(",")] if a.text_lens else []
+if text_lens:
+    a.batches, a.text = str(len(text_lens)), max(text_lens)
 cfg = dict(synth.DEFAULT_MODEL_CONFIG, n_text=60, n_flows=2)
 m = flowtron.Flowtron(**cfg)
 m.load_state_dict(synth.make_state_dict(cfg, seed=17))
@@ -32,15 +39,34 @@ text = torch.randint(1, 60, (Bmax, a.text), generator=g).cuda()
 spk = torch.zeros(Bmax, dtype=torch.long).cuda()
 
 
-def run(B, batched):
+def run(B, batched, in_lens=None):
     os.environ["FLOWTRON_DECODE_BATCH"] = "1" if batched else "0"
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    m.infer(residual[:B], spk[:B], text[:B], gate_threshold=1.0)
+    m.infer(residual[:B], spk[:B], text[:B], gate_threshold=1.0, in_lens=in_lens)
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1)
 
+
+if text_lens:
+    B = len(text_lens)
+    ways = {"ragged batch": (True, text_lens), "loop over trimmed": (False, text_lens), "unragged batch at L %d" % a.text: (True, None)}
+    for mode in a.modes.split(","):
+        os.environ["FLOWTRON_MFMA"] = mode
+        for _ in range(a.warmup):
+            for w in ways.values():
+                run(B, *w)
+        ms = {k: [] for k in ways}
+        for _ in range(a.reps):
+            for k, w in ways.items():                            # alternate: drift hits every way alike
+                ms[k].append(run(B, *w))
+        for k in ways:
+            t = np.array(ms[k])
+            med = float(np.median(t))
+            print("%s B=%d text %s %s: infer median %.2f ms (min %.2f, max %.2f, %d runs), %.1f us per frame and flow"
+                  % (mode, B, a.text_lens, k, med, t.min(), t.max(), a.reps, med * 1e3 / (a.frames * cfg["n_flows"])), flush=True)
+    sys.exit(0)
 
 for mode in a.modes.split(","):
     os.environ["FLOWTRON_MFMA"] = mode

@@ -96,7 +96,8 @@ def griffin_lim(magnitudes, stft_fn, n_iters=30):
     """audio_processing.py:59-75 on the device.  magnitudes [B, n_fft/2+1, T] (device tensor), stft_fn an STFT.
     The starting angles are drawn on the host exactly as the reference draws them (np.random.rand, so np.random.seed(s)
     gives the reference's starting point) and copied to the device once; then n_iters x (ft_stft_r8 for the phase +
-    ft_istft_r8) run without a host synchronisation.  Returns [B, hop * (T - 1)]."""
+    ft_istft_r8, or ft_stft_pow2 + ft_istft_pow2 off the 1024 setting) run without a host synchronisation.
+    Returns [B, hop * (T - 1)]."""
     L.require_cuda(magnitudes)
     stft_fn._check_spectrum(magnitudes, magnitudes)
     T = magnitudes.shape[-1]
@@ -136,10 +137,15 @@ def filterbank_csr(mel_basis: np.ndarray):
     return np.asarray(bin0, np.int32), np.asarray(ptr, np.int32), np.asarray(w, np.float32)
 
 
+POW2_NFFT = (256, 512, 1024, 2048, 4096)      # the analysis sizes of csrc/stft_pow2.hip
+
+
 class STFT(torch.nn.Module):
     """The reference STFT (audio_processing.py:172-270): `transform(y)` -> (magnitude, phase), both [B, n_fft/2+1, N // hop + 1]
     (real FFT, ft_stft_r8), `inverse(magnitude, phase)` -> [B, 1, hop * (T - 1)] (inverse real FFT + overlap-add, ft_istft_r8)
-    and `forward(y)` = inverse(transform(y)); one HIP kernel each (csrc/stft_r8.hip)."""
+    and `forward(y)` = inverse(transform(y)); one HIP kernel each (csrc/stft_r8.hip).  fast_path(): n_fft 1024, hop <= 256;
+    pow2_path(): every other n_fft in POW2_NFFT with 1 <= hop <= win_length <= n_fft (ft_stft_pow2 / ft_istft_pow2,
+    csrc/stft_pow2.hip); any other setting raises NotImplementedError."""
 
     def __init__(self, filter_length=800, hop_length=200, win_length=800, window="hann"):
         super().__init__()
@@ -150,11 +156,23 @@ class STFT(torch.nn.Module):
     def fast_path(self):
         return self.filter_length == 1024 and self.hop_length <= 256
 
+    def pow2_path(self):
+        """The settings the power-of-two kernels (csrc/stft_pow2.hip) take that fast_path() does not: n_fft in POW2_NFFT and
+        1 <= hop <= win_length <= n_fft."""
+        return (not self.fast_path() and self.filter_length in POW2_NFFT
+                and 1 <= self.hop_length <= self.win_length <= self.filter_length)
+
+    def _require_device_path(self, what):
+        if not (self.fast_path() or self.pow2_path()):
+            raise NotImplementedError(
+                "%s runs on the device for filter_length in %s with 1 <= hop_length <= win_length <= filter_length (and for "
+                "filter_length 1024 with any hop_length <= 256); got filter_length %d, hop_length %d, win_length %d"
+                % (what, "/".join(map(str, POW2_NFFT)), self.filter_length, self.hop_length, self.win_length))
+
     def transform(self, input_data):
         """audio_processing.py:207-235."""
         L.require_cuda(input_data)
-        if not self.fast_path():
-            raise NotImplementedError("STFT.transform is built for filter_length 1024 / hop <= 256 (config.json:32-34)")
+        self._require_device_path("STFT.transform")
         y = input_data.contiguous().float()
         if self.fft_window.device != y.device:
             self.to(y.device)
@@ -162,20 +180,23 @@ class STFT(torch.nn.Module):
         n_frames = N // self.hop_length + 1
         mag = torch.empty(B, self.filter_length // 2 + 1, n_frames, device=y.device, dtype=torch.float32)
         phase = torch.empty_like(mag)
-        L.check(L.lib().ft_stft_r8(L.ptr(y), L.ptr(self.fft_window), None, None, None, None, L.ptr(mag), L.ptr(phase), B, N,
-                                   self.hop_length, 0, L.stream()), "ft_stft_r8")
+        if self.fast_path():
+            L.check(L.lib().ft_stft_r8(L.ptr(y), L.ptr(self.fft_window), None, None, None, None, L.ptr(mag), L.ptr(phase), B,
+                                       N, self.hop_length, 0, L.stream()), "ft_stft_r8")
+        else:
+            L.check(L.lib().ft_stft_pow2(L.ptr(y), L.ptr(self.fft_window), None, None, None, None, L.ptr(mag), L.ptr(phase), B,
+                                         N, self.filter_length, self.hop_length, self.win_length, 0, L.stream()), "ft_stft_pow2")
         return mag, phase
 
     def _check_spectrum(self, magnitude, phase):
-        if not self.fast_path():
-            raise NotImplementedError("STFT.inverse is built for filter_length 1024 / hop <= 256 (config.json:32-34)")
+        self._require_device_path("STFT.inverse")
         nb = self.filter_length // 2 + 1
         if magnitude.dim() != 3 or magnitude.shape[1] != nb or phase.shape != magnitude.shape:
             raise ValueError("STFT.inverse needs magnitude and phase of one shape [B, %d, T], got %s and %s"
                              % (nb, tuple(magnitude.shape), tuple(phase.shape)))
 
     def inverse(self, magnitude, phase):
-        """audio_processing.py:237-263: [B, n_fft/2+1, T] x 2 -> [B, 1, hop * (T - 1)] (ft_istft_r8)."""
+        """audio_processing.py:237-263: [B, n_fft/2+1, T] x 2 -> [B, 1, hop * (T - 1)] (ft_istft_r8 / ft_istft_pow2)."""
         L.require_cuda(magnitude, phase)
         self._check_spectrum(magnitude, phase)
         m, ph = magnitude.contiguous().float(), phase.contiguous().float()
@@ -183,9 +204,12 @@ class STFT(torch.nn.Module):
             self.to(m.device)
         B, _, T = m.shape
         y = torch.empty(B, 1, self.hop_length * max(T - 1, 0), device=m.device, dtype=torch.float32)
-        if T >= 2:                                      # one frame leaves nothing after the two 512-sample trims
+        if T >= 2 and self.fast_path():                 # one frame leaves nothing after the two n_fft/2-sample trims
             L.check(L.lib().ft_istft_r8(L.ptr(m), L.ptr(ph), L.ptr(self.fft_window), L.ptr(y), B, T, self.hop_length,
                                         L.stream()), "ft_istft_r8")
+        elif T >= 2:
+            L.check(L.lib().ft_istft_pow2(L.ptr(m), L.ptr(ph), L.ptr(self.fft_window), L.ptr(y), B, T, self.filter_length,
+                                          self.hop_length, self.win_length, L.stream()), "ft_istft_pow2")
         return y
 
     def forward(self, input_data):
@@ -218,7 +242,7 @@ class TacotronSTFT(torch.nn.Module):
         return dynamic_range_decompression(magnitudes)
 
     def mel_spectrogram_ragged(self, y, n_samples, max_t=None):
-        """The collated batch of the data path in one launch (ft_stft_r8_ragged): y [B,N] zero-padded audio on the device,
+        """The collated batch of the data path in one launch (ft_stft_r8_ragged / ft_stft_pow2_ragged): y [B,N] zero-padded audio on the device,
         n_samples [B] (int32, device) -> [B, n_mel_channels, max_t]; utterance b's frames t < n_samples[b] // hop + 1 equal
         mel_spectrogram(y[b:b+1, :n_samples[b]]), later frames are zero (DataCollate's padding, data.py:215-229)."""
         L.require_cuda(y, n_samples)
@@ -228,13 +252,25 @@ class TacotronSTFT(torch.nn.Module):
         B, N = y.shape
         st = self.stft_fn
         T_out = N // st.hop_length + 1 if max_t is None else int(max_t)
-        if not (st.fast_path() and self.n_mel_channels <= 128 and N > st.filter_length // 2):
-            raise NotImplementedError("the ragged front end is built for n_fft = 1024, hop <= 256 (config.json:32-34)")
+        if not (self.ragged_path() and N > st.filter_length // 2):
+            raise NotImplementedError("the ragged front end is built for n_mel_channels <= 128 and n_fft = 1024 with hop <= 256, "
+                                      "or n_fft in %s with 1 <= hop <= win_length <= n_fft" % (POW2_NFFT,))
         mel = torch.empty(B, self.n_mel_channels, T_out, device=y.device, dtype=torch.float32)
-        L.check(L.lib().ft_stft_r8_ragged(L.ptr(y), L.ptr(n_samples.to(torch.int32)), L.ptr(st.fft_window), L.ptr(self.fb_bin0),
-                                          L.ptr(self.fb_ptr), L.ptr(self.fb_w), L.ptr(mel), B, N, st.hop_length, self.n_mel_channels,
-                                          T_out, L.stream()), "ft_stft_r8_ragged")
+        ns = n_samples.to(torch.int32)
+        if st.fast_path():
+            L.check(L.lib().ft_stft_r8_ragged(L.ptr(y), L.ptr(ns), L.ptr(st.fft_window), L.ptr(self.fb_bin0), L.ptr(self.fb_ptr),
+                                              L.ptr(self.fb_w), L.ptr(mel), B, N, st.hop_length, self.n_mel_channels, T_out,
+                                              L.stream()), "ft_stft_r8_ragged")
+        else:
+            L.check(L.lib().ft_stft_pow2_ragged(L.ptr(y), L.ptr(ns), L.ptr(st.fft_window), L.ptr(self.fb_bin0), L.ptr(self.fb_ptr),
+                                                L.ptr(self.fb_w), L.ptr(mel), B, N, st.filter_length, st.hop_length, st.win_length,
+                                                self.n_mel_channels, T_out, L.stream()), "ft_stft_pow2_ragged")
         return mel
+
+    def ragged_path(self):
+        """True when mel_spectrogram_ragged (one launch per batch) takes this setting: the rFFT kernels of fast_path() or
+        pow2_path() with n_mel_channels <= 128."""
+        return (self.stft_fn.fast_path() or self.stft_fn.pow2_path()) and self.n_mel_channels <= 128
 
     def mel_spectrogram(self, y):
         """y [B,N] float32 in [-1,1] (device tensor) -> [B, n_mel_channels, N // hop + 1]."""
@@ -255,6 +291,11 @@ class TacotronSTFT(torch.nn.Module):
             # rFFT (512-point complex FFT + split) + sparse triangular filterbank, one wave per frame (csrc/stft_r8.hip)
             L.check(L.lib().ft_stft_r8(L.ptr(y), L.ptr(st.fft_window), L.ptr(self.fb_bin0), L.ptr(self.fb_ptr), L.ptr(self.fb_w),
                                        L.ptr(mel), None, None, B, N, st.hop_length, self.n_mel_channels, L.stream()), "ft_stft_r8")
+        elif st.pow2_path() and self.n_mel_channels <= 128 and N > st.filter_length // 2:
+            # the same rFFT design for any power-of-two n_fft and hop (csrc/stft_pow2.hip); mel_spectrogram_ragged shares it
+            L.check(L.lib().ft_stft_pow2(L.ptr(y), L.ptr(st.fft_window), L.ptr(self.fb_bin0), L.ptr(self.fb_ptr), L.ptr(self.fb_w),
+                                         L.ptr(mel), None, None, B, N, st.filter_length, st.hop_length, st.win_length,
+                                         self.n_mel_channels, L.stream()), "ft_stft_pow2")
         else:                                           # general n_fft: complex radix-2 FFT + dense filterbank (csrc/stft.hip)
             L.check(L.lib().ft_stft_mel(L.ptr(y), L.ptr(st.fft_window), L.ptr(self.mel_basis), L.ptr(mel), B, N,
                                         st.filter_length, st.hop_length, self.n_mel_channels, L.stream()), "ft_stft_mel")

@@ -546,6 +546,18 @@ int ft_stft_r8_ragged(const float* y, const int32_t* n_samples, const float* win
  * the window's sum-square envelope where that is > FLT_MIN, first and last 512 samples cut.  Deterministic: no atomics, each
  * sample sums its frames in ascending t.  window: hann [1024] as ft_stft_r8.  T >= 2. */
 int ft_istft_r8(const float* mag, const float* phase, const float* window, float* y, int B, int T, int hop, void* stream);
+/* The same three for every power-of-two analysis size n_fft = 256 .. 4096 and any hop (csrc/stft_pow2.hip): an n_fft/2-point
+ * complex FFT (Stockham, one radix-2 / -4 pass and radix-8 passes, one wave per frame) plus the split step.  Bins: n_fft/2+1.
+ * 1 <= hop <= win_length <= n_fft; window: hann [n_fft] (win_length zero-padded by the caller); N > n_fft / 2.  Outputs, the
+ * ragged form and the inverse's rules (ascending-t overlap-add, wss in the kernel, > FLT_MIN, both n_fft/2 trims) as above.
+ * Arguments outside that scope: FT_EINVAL before any device call. */
+int ft_stft_pow2(const float* y, const float* window, const int32_t* band_bin0, const int32_t* band_ptr, const float* band_w,
+                 float* mel, float* mag, float* phase, int B, int N, int n_fft, int hop, int win_length, int n_mel, void* stream);
+int ft_stft_pow2_ragged(const float* y, const int32_t* n_samples, const float* window, const int32_t* band_bin0,
+                        const int32_t* band_ptr, const float* band_w, float* mel, int B, int N, int n_fft, int hop, int win_length,
+                        int n_mel, int T_out, void* stream);
+int ft_istft_pow2(const float* mag, const float* phase, const float* window, float* y, int B, int T, int n_fft, int hop,
+                  int win_length, void* stream);
 
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with

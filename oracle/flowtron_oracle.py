@@ -414,7 +414,7 @@ def ar_step_infer(sd: SD, pfx: str, residual, enc, has_gate, temperature=1.0, ga
         p = torch.softmax(e, dim=1)
         if attns is not None:                                              # forced alignment, flowtron.py:585-588
             p = attns[i].reshape(1, -1)
-        elif attn_prior is not None:
+        elif attn_prior is not None:               # (tests/decode_ref64.F64Prior relies on this exact access: attn_prior[:, i].float())
             p = torch.softmax(torch.log(p + 1e-20) + torch.log(attn_prior[:, i].float() + 1e-20), dim=1)
         if cumm_on:
             prev_attn = p[:, None, :]

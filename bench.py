@@ -12,9 +12,13 @@ all-reduce(AVG) of the flat gradient arena at the end of backward when N > 1; pe
 attention prior + CTC on, bf16 MFMA operands with fp32 accumulate/storage.  Weak scaling: every rank processes its
 own 32 utterances.  value = valid mel frames (sum of out_lens over all ranks and steps) / wall time.
 
-Rank 0 prints ONE JSON line.  `roofline` = the whole step against the MFMA roof; under it `dominant_kernel` / `second_kernel`
-(the persistent LSTM recurrences, timed live with HIP events on the launch stream next to the launch-per-step kernels they
-replace) carry their own bound: a per-step hand-off-latency floor, with the HBM and MFMA fractions beside it; `parity` (the HIP gradients of a batch slice against the CPU oracle), `cpu_baseline` (the oracle timed on this box's host
+Rank 0 prints ONE JSON line.  Without --full the run sets up, warms up, times the steps, writes --dump-outputs and prints the
+headline block (metric, value, unit, ms_per_step, dtype, config; `dp` when N > 1) -- nothing else runs.  --full adds every
+other leg after the timed region (minutes): `roofline` = the whole step against the MFMA roof; under it `dominant_kernel` /
+`second_kernel` (the persistent LSTM recurrences, timed live with HIP events on the launch stream next to the launch-per-step
+kernels they replace) carry their own bound: a per-step hand-off-latency floor, with the HBM and MFMA fractions beside it;
+`trainpy_step` (the step as the reference's train.py calls it, from a DataLoader); `stft` (the mel front end);
+`parity` (the HIP gradients of a batch slice against the CPU oracle), `cpu_baseline` (the oracle timed on the host's
 cores on a bounded sample), `infer` (RTF of a 400-frame 2-flow decode with 16-bit weight images, median of 7 calls) and
 `infer_fp32` (the same decode with fp32 weights and arithmetic -- the precision of the reference's inference.py).
 
@@ -795,14 +799,17 @@ def main():
                     help="ljs = BASELINE configs[1] (the headline line); libritts = configs[2] (123 speakers, L <= 237, bf16); "
                          "libritts_fp16 = configs[4] (fp16 operands + GradScaler, no attention prior); ljs_cumm = configs[1] with "
                          "use_cumm_attention (location-sensitive attention, SURVEY 8a row a17: the key projection is redone every frame)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-infer", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg of the line: parity, cpu_baseline, trainpy_step, the per-kernel "
+                         "roofline timings, infer / infer_fp32, stft (minutes; a run without it prints the headline block only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline and parity legs")
+    ap.add_argument("--no-infer", action="store_true", help="with --full: skip the infer, infer_fp32 and stft legs")
     ap.add_argument("--hidden", type=int, default=None,
                     help="n_hidden of the attention / decoder LSTMs (default: the config's 1024).  A variant of the workload, not the "
                          "BASELINE line: the roofline / parity / infer / trainpy legs are skipped")
     ap.add_argument("--no-pad-hidden", action="store_true",
                     help="with --hidden < 1024: the launch-per-step recurrence kernels instead of the zero-padded persistent ones (yardstick)")
-    ap.add_argument("--no-trainpy", action="store_true", help="skip the train.py-call-sequence block (trainpy_step)")
+    ap.add_argument("--no-trainpy", action="store_true", help="with --full: skip the train.py-call-sequence block (trainpy_step)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
@@ -892,7 +899,7 @@ def main():
         return loss
 
     hip_path = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "ljs":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "ljs":
         # parity of the benchmarked dtype: the HIP path on the oracle's bounded sample, with the initial weights (before any
         # update), dropout off like the oracle; the cpu_baseline worker compares (it holds the oracle's gradients)
         try:
@@ -1022,17 +1029,17 @@ def main():
             res["config"]["dump_outputs"] = ("the last timed step started from the run's initial state (weights, RAdam state, GradScaler, "
                                              "RNG): final_loss is that step's loss, not the loss after the earlier updates")
         n1_path = os.path.join(os.environ.get("TMPDIR", "/tmp"), "flowtron_bench_n1_%s.json" % args.config)
-        if world == 1:
+        if world == 1 and args.full:                         # (a run without --full leaves no file behind and reads none)
             try:
                 json.dump({"value": res["value"], "ms_per_step": res["ms_per_step"], "steps": args.steps}, open(n1_path, "w"))
             except OSError:
                 pass
-        else:
-            # self-diagnosing N > 1 line: what the collective cost on every rank, on which backend, beside the N = 1
-            # run of the same box when the driver ran it first (SCALE runs N = 1, 2, 4, 8 back to back)
+        elif world > 1:
+            # self-diagnosing N > 1 line: what the collective cost on every rank, on which backend, and with --full
+            # beside the N = 1 --full run of the same host when that ran first (a scaling series runs N = 1, 2, 4, 8 back to back)
             n1 = None
             try:
-                n1 = json.load(open(n1_path))
+                n1 = json.load(open(n1_path)) if args.full else None
             except (OSError, ValueError):
                 pass
             arena_mb = model._grad_arena.numel * 4 / 1e6
@@ -1048,161 +1055,162 @@ def main():
 
                          "note": "allreduce_ms = HIP events on the compute stream around the end-of-backward exchange (poison check + "
                                  "collective(s) + stream wait); with the end-of-backward regime all of it is exposed"}
-        mode = {"bf16": L.FT_BF16, "f16": L.FT_F16, "f32": L.FT_F32}[args.mfma]
-        if world == 1 and not args.no_trainpy and args.config in ("ljs", "libritts"):
-            try:
-                log("train.py call sequence (DataLoader -> .cuda() -> zero_grad -> fwd -> 4x item -> bwd -> torch clip -> step) ...")
-                res["trainpy_step"] = trainpy_step_block(model, criterion, optimizer, batch_cpu, min(args.steps, 20), 3, use_prior)
-                res["trainpy_step"]["gap_to_headline_ms"] = round(res["trainpy_step"]["ms_per_step"] - res["ms_per_step"], 2)
-            except Exception as e:
-                res["trainpy_step"] = {"error": repr(e)}
-        log("roofline kernel timing ...")
-        # Top level: the WHOLE STEP against the MFMA roof: valid frames/s x 325 MFLOP of algorithmic work per valid frame
-        # (2 flows, forward + backward, padding and the tanh recomputation not counted) over the dense bf16 peak.  The step is a chain
-        # of latency-bound recurrences with GEMMs in between, so the dominant KERNELS are reported under their own bound below it.
-        frames_per_gpu = res["value"] / world
-        res["roofline"] = {"bound": "mfma", "scope": "whole training step", "achieved": round(frames_per_gpu * 325e6 / 1e12, 2),
-                           "peak": 2500.0, "unit": "TFLOP/s", "frac": round(frames_per_gpu * 325e6 / 2.5e15, 5), "traffic": None,
-                           "flop_per_valid_frame": 325e6,
-                           "gemm_mfma_busy_frac_pmc": {k: dict(zip(("frac", "pmc_round"), pmc_value("MFMA_BUSY", k, "mfma_busy_frac", with_source=True)))
-                                                       for k in ("gemm_bf16_k<true, true, true, 256, 32, false>", "gemm_bf16_k<false, true, false, 128, 64, true>",
-                                                                 "gemm_bf16_k<false, false, false, 128, 64, true>",
-                                                                 "gemm_bf16_k<false, false, false, 128, 32, false>")}}
-        if args.config == "ljs_cumm":
-            try:
-                res["roofline"]["cumulative_attention"] = cumm_roofline(args.batch, batch_cpu["in_lens"], mode)
-            except Exception as e:
-                res["roofline"]["cumulative_attention"] = {"error": repr(e)}
-        variant = model_config["n_hidden"] != MODEL_CONFIG["n_hidden"]
-        if variant:           # (a workload variant: the 325 MFLOP per frame and the kernel legs below describe the BASELINE model)
-            res["roofline"] = {"bound": "mfma", "achieved": None, "peak": 2500.0, "unit": "TFLOP/s", "frac": None, "traffic": None,
-                               "note": "--hidden variant: not priced (the roofline legs describe the n_hidden = 1024 model)"}
-        try:
-            if variant:
-                raise RuntimeError("skipped for a --hidden variant")
-            from flowtron_amd import ops as _ops
-            _dev = torch.device("cuda", torch.cuda.current_device())
-            _slices = _ops.lstm_persist_slices(args.batch, MODEL_CONFIG["n_hidden"], False, mode, _dev)
-            if _ops.lstm_persist_groups(args.batch, MODEL_CONFIG["n_hidden"], False, mode, _dev) or _slices:
-                # dominant kernels of the step: the persistent recurrences (backward: six launches per step; forward: the attention
-                # LSTM's launch + the decoder pair's role pipeline per flow) -- for --batch > 32 the first slice of 32 rows is timed
-                n_sl = (args.batch + 31) // 32 if _slices else 1      # (share estimate only: a wider batch runs 8 / 16 rows per group)
-                dom, second = persist_roofline(min(args.batch, 32), MODEL_CONFIG["n_hidden"], T, batch_cpu["out_lens"][:32], mode)
-                for blk in (dom, second):
-                    blk["share_of_step"] = round(n_sl * blk["us_per_training_step"] * 1e-3 / res["ms_per_step"], 3)
-                    if n_sl > 1:
-                        blk["launches_per_sequence"] = n_sl
-                if second["share_of_step"] > dom["share_of_step"]:       # dominant = the larger share of the step
-                    dom, second = second, dom
-                res["roofline"]["dominant_kernel"], res["roofline"]["second_kernel"] = dom, second
-            elif _ops.lstm2_supported(args.batch, MODEL_CONFIG["n_hidden"], mode):
-                res["roofline"]["dominant_kernel"] = lstm2_step_roofline(args.batch, MODEL_CONFIG["n_hidden"], T)
-                res["roofline"]["second_kernel"] = lstm_step_roofline(args.batch, MODEL_CONFIG["n_hidden"], T, mode)
-            else:
-                res["roofline"]["dominant_kernel"] = lstm_step_roofline(args.batch, MODEL_CONFIG["n_hidden"], T, mode)
-        except Exception as e:                      # never lose the headline number to the side measurement
-            res["roofline"]["dominant_kernel"] = {"error": repr(e)}
-        if world == 1 and not args.no_infer and args.config == "ljs":
-            model.eval()
-            n_frames = int(os.environ.get("BENCH_INFER_FRAMES", "400"))      # (a PMC pass may shorten it)
-            z = torch.randn(1, 80, n_frames, device="cuda") * 0.5
-            text = b["text"][:1, :69]
-            spk = b["speaker_ids"][:1]
-            n_fl = MODEL_CONFIG["n_flows"]
-            hops = handoff_hops()
-
-            def time_infer(operands):
-                """median wall time of Flowtron.infer (400 frames, gate disabled) with the decoder of that operand mode"""
-                os.environ["FLOWTRON_MFMA"] = operands
+        if args.full:                                        # every other leg of the line: minutes of runs of their own
+            mode = {"bf16": L.FT_BF16, "f16": L.FT_F16, "f32": L.FT_F32}[args.mfma]
+            if world == 1 and not args.no_trainpy and args.config in ("ljs", "libritts"):
                 try:
-                    for _ in range(2):
-                        model.infer(z, spk, text, gate_threshold=1.0)       # warm-up (+ hipGraph capture / weight images)
-                    torch.cuda.synchronize()
-                    tis = []
-                    for _ in range(int(os.environ.get("BENCH_INFER_CALLS", "7"))):
-                        t1 = time.perf_counter()
-                        mel, _ = model.infer(z, spk, text, gate_threshold=1.0)
-                        torch.cuda.synchronize()
-                        tis.append(time.perf_counter() - t1)
-                finally:
-                    os.environ["FLOWTRON_MFMA"] = args.mfma
-                ti = sorted(tis)[len(tis) // 2]
-                nf = int(mel.shape[2])
-                return nf, ti, {"frames": nf, "seconds": round(ti, 5), "seconds_min": round(min(tis), 5), "seconds_max": round(max(tis), 5),
-                                "calls": len(tis), "frames_per_s": round(nf / ti, 1), "rtf": round(ti / (nf * HOP / SR), 5),
-                                "us_per_frame_per_flow": round(ti / nf / n_fl * 1e6, 2)}
+                    log("train.py call sequence (DataLoader -> .cuda() -> zero_grad -> fwd -> 4x item -> bwd -> torch clip -> step) ...")
+                    res["trainpy_step"] = trainpy_step_block(model, criterion, optimizer, batch_cpu, min(args.steps, 20), 3, use_prior)
+                    res["trainpy_step"]["gap_to_headline_ms"] = round(res["trainpy_step"]["ms_per_step"] - res["ms_per_step"], 2)
+                except Exception as e:
+                    res["trainpy_step"] = {"error": repr(e)}
+            log("roofline kernel timing ...")
+            # Top level: the WHOLE STEP against the MFMA roof: valid frames/s x 325 MFLOP of algorithmic work per valid frame
+            # (2 flows, forward + backward, padding and the tanh recomputation not counted) over the dense bf16 peak.  The step is a chain
+            # of latency-bound recurrences with GEMMs in between, so the dominant KERNELS are reported under their own bound below it.
+            frames_per_gpu = res["value"] / world
+            res["roofline"] = {"bound": "mfma", "scope": "whole training step", "achieved": round(frames_per_gpu * 325e6 / 1e12, 2),
+                               "peak": 2500.0, "unit": "TFLOP/s", "frac": round(frames_per_gpu * 325e6 / 2.5e15, 5), "traffic": None,
+                               "flop_per_valid_frame": 325e6,
+                               "gemm_mfma_busy_frac_pmc": {k: dict(zip(("frac", "pmc_round"), pmc_value("MFMA_BUSY", k, "mfma_busy_frac", with_source=True)))
+                                                           for k in ("gemm_bf16_k<true, true, true, 256, 32, false>", "gemm_bf16_k<false, true, false, 128, 64, true>",
+                                                                     "gemm_bf16_k<false, false, false, 128, 64, true>",
+                                                                     "gemm_bf16_k<false, false, false, 128, 32, false>")}}
+            if args.config == "ljs_cumm":
+                try:
+                    res["roofline"]["cumulative_attention"] = cumm_roofline(args.batch, batch_cpu["in_lens"], mode)
+                except Exception as e:
+                    res["roofline"]["cumulative_attention"] = {"error": repr(e)}
+            variant = model_config["n_hidden"] != MODEL_CONFIG["n_hidden"]
+            if variant:           # (a workload variant: the 325 MFLOP per frame and the kernel legs below describe the BASELINE model)
+                res["roofline"] = {"bound": "mfma", "achieved": None, "peak": 2500.0, "unit": "TFLOP/s", "frac": None, "traffic": None,
+                                   "note": "--hidden variant: not priced (the roofline legs describe the n_hidden = 1024 model)"}
             try:
-                log("inference RTF (16-bit weight images, persistent decode) ...")
-                nf, ti, blk = time_infer(args.mfma)
-                # dec_persist_k streams nothing per frame (the flow's weights are register-resident), so neither HBM nor MFMA bounds
-                # it: a frame is 9 dependent stages, each ending in a hand-off of its output vector -- 5 chip-wide (h_att, h0, h1, u1,
-                # u2: one fabric hop into every XCD + one L2 hop to every CU) and 4 XCD-local (query, scores, context, conv output)
-                floor = 5 * (hops["cross_xcd_hop_us"] + hops["same_xcd_hop_us"]) + 4 * hops["same_xcd_hop_us"]
-                per = ti / nf / n_fl * 1e6
-                blk["roofline"] = {"bound": "handoff-latency", "stages_per_frame": 9, "floor_us_per_frame_per_flow": round(floor, 2),
-                                   "us_per_frame_per_flow": round(per, 2), "frac": round(floor / per, 3),
-                                   "note": "floor = 5 x (cross-XCD hop + same-XCD hop) + 4 x same-XCD hop from profiles/r02_handoff_hops.json; the "
-                                           "GEMV arithmetic of a stage (VALU, 26.8 M weights over 1024 waves) and host-side launch / "
-                                           "result copies are what frac leaves"}
-                blk["config"] = "2-flow LJS, B=1, L=69, sigma=0.5, %s images of the weights (NARROWER than the reference's fp32 inference.py; see infer_fp32), gate disabled" % args.mfma
-                res["infer"] = blk
-            except Exception as e:
-                res["infer"] = {"error": repr(e)}
-            try:
-                log("inference RTF (fp32 weights: the reference's precision) ...")
-                nf, ti, blk = time_infer("f32")
-                wbytes = 26838656 * 4                                   # SURVEY 8d: weights a frame of one flow must read, fp32
-                ach = n_fl * wbytes * nf / ti / 1e9
-                persist32 = os.environ.get("FLOWTRON_DECODE_PERSIST", "1") != "0"
-                persist32_flag = lambda: persist32
-                per32 = ti / nf / n_fl * 1e6
-                floor32 = 5 * (hops["cross_xcd_hop_us"] + hops["same_xcd_hop_us"]) + 4 * hops["same_xcd_hop_us"]
-                # (VERDICT r5 #10) with the persistent launch NOTHING of this streams per frame: `achieved` is an EQUIVALENT bandwidth -- what a
-                # decoder that streamed the flow's fp32 weights every frame would have to sustain to be as fast -- not a measured one.
-                # The bound that describes the kernel is the one `infer` uses: 9 dependent stages per frame.
-                blk["roofline"] = {"bound": "handoff-latency" if persist32_flag() else "hbm",
-                                   "stages_per_frame": 9, "floor_us_per_frame_per_flow": round(floor32, 2), "us_per_frame_per_flow": round(per32, 2),
-                                   "frac": round(floor32 / per32, 3) if persist32_flag() else round(ach / 8000.0, 4),
-                                   "equivalent_bandwidth": {"kind": "EQUIVALENT, not measured: algorithmic fp32 weight bytes per frame / frame time",
-                                                            "achieved": round(ach, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(ach / 8000.0, 4)},
-                                   "bytes_per_frame_per_flow": wbytes,
-                                   "note": ("algorithmic weight bytes per frame over the frame time.  dec_persist_k<true>: one launch per flow; the "
-                                            "recurrent / large LSTM matrices (16.8 M of the 26.8 M weights) never move -- they are register-resident "
-                                            "for the whole utterance --, the other 40 MB per frame and flow (query rows and the 1x1 conv once per XCD) "
-                                            "are re-read from the L2 / Infinity Cache under the stage hand-offs")
-                                   if persist32 else
-                                   "fp32 weights streamed every frame by the staged hipGraph chain (L2 / Infinity Cache resident after the first frame)"}
-                blk["config"] = ("2-flow LJS, B=1, L=69, sigma=0.5, fp32 weights and arithmetic = the reference's inference.py:68-71 "
-                                 "(no autocast), %s, gate disabled" % ("one persistent launch per flow (dec_persist_k<true>)" if persist32
-                                                                        else "staged hipGraph decode chain"))
-                if persist32:                                           # the staged chain it replaces, timed beside it
-                    os.environ["FLOWTRON_DECODE_PERSIST"] = "0"
+                if variant:
+                    raise RuntimeError("skipped for a --hidden variant")
+                from flowtron_amd import ops as _ops
+                _dev = torch.device("cuda", torch.cuda.current_device())
+                _slices = _ops.lstm_persist_slices(args.batch, MODEL_CONFIG["n_hidden"], False, mode, _dev)
+                if _ops.lstm_persist_groups(args.batch, MODEL_CONFIG["n_hidden"], False, mode, _dev) or _slices:
+                    # dominant kernels of the step: the persistent recurrences (backward: six launches per step; forward: the attention
+                    # LSTM's launch + the decoder pair's role pipeline per flow) -- for --batch > 32 the first slice of 32 rows is timed
+                    n_sl = (args.batch + 31) // 32 if _slices else 1      # (share estimate only: a wider batch runs 8 / 16 rows per group)
+                    dom, second = persist_roofline(min(args.batch, 32), MODEL_CONFIG["n_hidden"], T, batch_cpu["out_lens"][:32], mode)
+                    for blk in (dom, second):
+                        blk["share_of_step"] = round(n_sl * blk["us_per_training_step"] * 1e-3 / res["ms_per_step"], 3)
+                        if n_sl > 1:
+                            blk["launches_per_sequence"] = n_sl
+                    if second["share_of_step"] > dom["share_of_step"]:       # dominant = the larger share of the step
+                        dom, second = second, dom
+                    res["roofline"]["dominant_kernel"], res["roofline"]["second_kernel"] = dom, second
+                elif _ops.lstm2_supported(args.batch, MODEL_CONFIG["n_hidden"], mode):
+                    res["roofline"]["dominant_kernel"] = lstm2_step_roofline(args.batch, MODEL_CONFIG["n_hidden"], T)
+                    res["roofline"]["second_kernel"] = lstm_step_roofline(args.batch, MODEL_CONFIG["n_hidden"], T, mode)
+                else:
+                    res["roofline"]["dominant_kernel"] = lstm_step_roofline(args.batch, MODEL_CONFIG["n_hidden"], T, mode)
+            except Exception as e:                      # never lose the headline number to the side measurement
+                res["roofline"]["dominant_kernel"] = {"error": repr(e)}
+            if world == 1 and not args.no_infer and args.config == "ljs":
+                model.eval()
+                n_frames = int(os.environ.get("BENCH_INFER_FRAMES", "400"))      # (a PMC pass may shorten it)
+                z = torch.randn(1, 80, n_frames, device="cuda") * 0.5
+                text = b["text"][:1, :69]
+                spk = b["speaker_ids"][:1]
+                n_fl = MODEL_CONFIG["n_flows"]
+                hops = handoff_hops()
+
+                def time_infer(operands):
+                    """median wall time of Flowtron.infer (400 frames, gate disabled) with the decoder of that operand mode"""
+                    os.environ["FLOWTRON_MFMA"] = operands
                     try:
-                        _, ti_s, blk_s = time_infer("f32")
-                        blk["replaces"] = {"decoder": "staged hipGraph chain (8 launches per frame)", "rtf": blk_s["rtf"],
-                                           "us_per_frame_per_flow": blk_s["us_per_frame_per_flow"]}
+                        for _ in range(2):
+                            model.infer(z, spk, text, gate_threshold=1.0)       # warm-up (+ hipGraph capture / weight images)
+                        torch.cuda.synchronize()
+                        tis = []
+                        for _ in range(int(os.environ.get("BENCH_INFER_CALLS", "7"))):
+                            t1 = time.perf_counter()
+                            mel, _ = model.infer(z, spk, text, gate_threshold=1.0)
+                            torch.cuda.synchronize()
+                            tis.append(time.perf_counter() - t1)
                     finally:
-                        os.environ["FLOWTRON_DECODE_PERSIST"] = "1"
-                res["infer_fp32"] = blk
-            except Exception as e:
-                res["infer_fp32"] = {"error": repr(e)}
-        if world == 1 and not args.no_infer and args.config == "ljs":
-            try:
-                res["stft"] = stft_block()
-            except Exception as e:
-                res["stft"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline and args.config == "ljs":
-            try:
-                log("cpu baseline (oracle, bounded sample) ...")
-                cb = cpu_baseline(args.batch, 1234 + 7 + rank, hip_path=hip_path)
-                if "parity" in cb:
-                    res["parity"] = cb.pop("parity")
-                res["cpu_baseline"] = cb
-            except Exception as e:
-                res["cpu_baseline"] = {"error": repr(e)}
-            finally:
-                if hip_path and os.path.exists(hip_path):
-                    os.remove(hip_path)
+                        os.environ["FLOWTRON_MFMA"] = args.mfma
+                    ti = sorted(tis)[len(tis) // 2]
+                    nf = int(mel.shape[2])
+                    return nf, ti, {"frames": nf, "seconds": round(ti, 5), "seconds_min": round(min(tis), 5), "seconds_max": round(max(tis), 5),
+                                    "calls": len(tis), "frames_per_s": round(nf / ti, 1), "rtf": round(ti / (nf * HOP / SR), 5),
+                                    "us_per_frame_per_flow": round(ti / nf / n_fl * 1e6, 2)}
+                try:
+                    log("inference RTF (16-bit weight images, persistent decode) ...")
+                    nf, ti, blk = time_infer(args.mfma)
+                    # dec_persist_k streams nothing per frame (the flow's weights are register-resident), so neither HBM nor MFMA bounds
+                    # it: a frame is 9 dependent stages, each ending in a hand-off of its output vector -- 5 chip-wide (h_att, h0, h1, u1,
+                    # u2: one fabric hop into every XCD + one L2 hop to every CU) and 4 XCD-local (query, scores, context, conv output)
+                    floor = 5 * (hops["cross_xcd_hop_us"] + hops["same_xcd_hop_us"]) + 4 * hops["same_xcd_hop_us"]
+                    per = ti / nf / n_fl * 1e6
+                    blk["roofline"] = {"bound": "handoff-latency", "stages_per_frame": 9, "floor_us_per_frame_per_flow": round(floor, 2),
+                                       "us_per_frame_per_flow": round(per, 2), "frac": round(floor / per, 3),
+                                       "note": "floor = 5 x (cross-XCD hop + same-XCD hop) + 4 x same-XCD hop from profiles/r02_handoff_hops.json; the "
+                                               "GEMV arithmetic of a stage (VALU, 26.8 M weights over 1024 waves) and host-side launch / "
+                                               "result copies are what frac leaves"}
+                    blk["config"] = "2-flow LJS, B=1, L=69, sigma=0.5, %s images of the weights (NARROWER than the reference's fp32 inference.py; see infer_fp32), gate disabled" % args.mfma
+                    res["infer"] = blk
+                except Exception as e:
+                    res["infer"] = {"error": repr(e)}
+                try:
+                    log("inference RTF (fp32 weights: the reference's precision) ...")
+                    nf, ti, blk = time_infer("f32")
+                    wbytes = 26838656 * 4                                   # SURVEY 8d: weights a frame of one flow must read, fp32
+                    ach = n_fl * wbytes * nf / ti / 1e9
+                    persist32 = os.environ.get("FLOWTRON_DECODE_PERSIST", "1") != "0"
+                    persist32_flag = lambda: persist32
+                    per32 = ti / nf / n_fl * 1e6
+                    floor32 = 5 * (hops["cross_xcd_hop_us"] + hops["same_xcd_hop_us"]) + 4 * hops["same_xcd_hop_us"]
+                    # (VERDICT r5 #10) with the persistent launch NOTHING of this streams per frame: `achieved` is an EQUIVALENT bandwidth -- what a
+                    # decoder that streamed the flow's fp32 weights every frame would have to sustain to be as fast -- not a measured one.
+                    # The bound that describes the kernel is the one `infer` uses: 9 dependent stages per frame.
+                    blk["roofline"] = {"bound": "handoff-latency" if persist32_flag() else "hbm",
+                                       "stages_per_frame": 9, "floor_us_per_frame_per_flow": round(floor32, 2), "us_per_frame_per_flow": round(per32, 2),
+                                       "frac": round(floor32 / per32, 3) if persist32_flag() else round(ach / 8000.0, 4),
+                                       "equivalent_bandwidth": {"kind": "EQUIVALENT, not measured: algorithmic fp32 weight bytes per frame / frame time",
+                                                                "achieved": round(ach, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(ach / 8000.0, 4)},
+                                       "bytes_per_frame_per_flow": wbytes,
+                                       "note": ("algorithmic weight bytes per frame over the frame time.  dec_persist_k<true>: one launch per flow; the "
+                                                "recurrent / large LSTM matrices (16.8 M of the 26.8 M weights) never move -- they are register-resident "
+                                                "for the whole utterance --, the other 40 MB per frame and flow (query rows and the 1x1 conv once per XCD) "
+                                                "are re-read from the L2 / Infinity Cache under the stage hand-offs")
+                                       if persist32 else
+                                       "fp32 weights streamed every frame by the staged hipGraph chain (L2 / Infinity Cache resident after the first frame)"}
+                    blk["config"] = ("2-flow LJS, B=1, L=69, sigma=0.5, fp32 weights and arithmetic = the reference's inference.py:68-71 "
+                                     "(no autocast), %s, gate disabled" % ("one persistent launch per flow (dec_persist_k<true>)" if persist32
+                                                                            else "staged hipGraph decode chain"))
+                    if persist32:                                           # the staged chain it replaces, timed beside it
+                        os.environ["FLOWTRON_DECODE_PERSIST"] = "0"
+                        try:
+                            _, ti_s, blk_s = time_infer("f32")
+                            blk["replaces"] = {"decoder": "staged hipGraph chain (8 launches per frame)", "rtf": blk_s["rtf"],
+                                               "us_per_frame_per_flow": blk_s["us_per_frame_per_flow"]}
+                        finally:
+                            os.environ["FLOWTRON_DECODE_PERSIST"] = "1"
+                    res["infer_fp32"] = blk
+                except Exception as e:
+                    res["infer_fp32"] = {"error": repr(e)}
+            if world == 1 and not args.no_infer and args.config == "ljs":
+                try:
+                    res["stft"] = stft_block()
+                except Exception as e:
+                    res["stft"] = {"error": repr(e)}
+            if world == 1 and not args.no_cpu_baseline and args.config == "ljs":
+                try:
+                    log("cpu baseline (oracle, bounded sample) ...")
+                    cb = cpu_baseline(args.batch, 1234 + 7 + rank, hip_path=hip_path)
+                    if "parity" in cb:
+                        res["parity"] = cb.pop("parity")
+                    res["cpu_baseline"] = cb
+                except Exception as e:
+                    res["cpu_baseline"] = {"error": repr(e)}
+                finally:
+                    if hip_path and os.path.exists(hip_path):
+                        os.remove(hip_path)
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()                       # rank 0 is still timing its roofline kernels: everybody leaves together

@@ -15,6 +15,6 @@ cp gpurun_out/pmc_r6/r06_pmc_*.json profiles/ 2>/dev/null
 bash scripts/profile_r6.sh "$TAG" > "$OUT/profile.log" 2>&1; head -n 12 "$OUT/profile.log"
 cd "$REPO"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$OUT/smoke.log" 2>&1; tail -n 2 "$OUT/smoke.log"
-timeout 900 python bench.py > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"; tail -c 2500 "$OUT/bench_line.json"
-for cfg in libritts libritts_fp16; do timeout 600 python bench.py --config $cfg --steps 30 --no-cpu-baseline --no-infer --no-trainpy > "$OUT/bench_line_$cfg.json" 2>> "$OUT/bench_stderr.log"; python -c "import json,sys; d=json.loads(open('$OUT/bench_line_$cfg.json').read().strip().splitlines()[-1]); print('$cfg', d['value'], d['ms_per_step'])"; done
-timeout 900 python bench.py --config ljs_cumm --no-cpu-baseline --no-infer --no-trainpy > "$OUT/bench_line_ljs_cumm.json" 2>> "$OUT/bench_stderr.log"; python -c "import json; d=json.loads(open('$OUT/bench_line_ljs_cumm.json').read().strip().splitlines()[-1]); print('ljs_cumm', d['value'], d['ms_per_step'])"
+timeout 900 python bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"; tail -c 2500 "$OUT/bench_line.json"
+for cfg in libritts libritts_fp16; do timeout 600 python bench.py --full --config $cfg --steps 30 --no-cpu-baseline --no-infer --no-trainpy > "$OUT/bench_line_$cfg.json" 2>> "$OUT/bench_stderr.log"; python -c "import json,sys; d=json.loads(open('$OUT/bench_line_$cfg.json').read().strip().splitlines()[-1]); print('$cfg', d['value'], d['ms_per_step'])"; done
+timeout 900 python bench.py --full --config ljs_cumm --no-cpu-baseline --no-infer --no-trainpy > "$OUT/bench_line_ljs_cumm.json" 2>> "$OUT/bench_stderr.log"; python -c "import json; d=json.loads(open('$OUT/bench_line_ljs_cumm.json').read().strip().splitlines()[-1]); print('ljs_cumm', d['value'], d['ms_per_step'])"

@@ -11,7 +11,7 @@ for C in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM
   [ "$TAG" = "SQ_INSTS_VALU" ] && TAG=VALU_TRANS
   [ "$TAG" = "SQ_WAVE_CYCLES" ] && TAG=WAVE_CYCLES
   rm -rf /tmp/pmc_run
-  timeout 300 rocprofv3 --pmc $C --output-format csv -d /tmp/pmc_run -o pmc -- python $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-trainpy --no-infer > "$OUT/pmc_${TAG}.log" 2>&1
+  timeout 300 rocprofv3 --pmc $C --output-format csv -d "$TMPDIR/pmc_run" -o pmc -- python $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-trainpy --no-infer > "$OUT/pmc_${TAG}.log" 2>&1
   echo "rocprof pmc [$C] exit $?" >> "$OUT/pmc_${TAG}.log"
   F=$(find /tmp/pmc_run -name "*counter_collection.csv" | head -1)
   [ -n "$F" ] && python "$REPO/scripts/pmc_summarize.py" "$F" "$OUT/r06_pmc_${TAG}.json" | head -3

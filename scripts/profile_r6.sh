@@ -5,7 +5,7 @@ REPO="${GRAFT_REPO_ROOT:-/root/repo}"
 OUT="$REPO/gpurun_out/prof_r6${1:+_$1}"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/kt2 && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt2 -o bench -- python $REPO/bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-infer --no-trainpy > "$OUT/train_under_rocprof.log" 2>&1
+rm -rf "$TMPDIR/kt2" && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$TMPDIR/kt2" -o bench -- python $REPO/bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-infer --no-trainpy > "$OUT/train_under_rocprof.log" 2>&1
 echo "rocprof kernel-trace exit $?" >> "$OUT/train_under_rocprof.log"
 TR=$(find /tmp/kt2 -name "*kernel_trace.csv" | head -1)
 cp $(find /tmp/kt2 -name "*kernel_stats.csv" | head -1) "$OUT/train_kernel_stats.csv" 2>/dev/null

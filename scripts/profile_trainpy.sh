@@ -5,7 +5,7 @@ REPO="${GRAFT_REPO_ROOT:-/root/repo}"
 OUT="$REPO/gpurun_out/prof_trainpy${1:+_$1}"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rm -rf /tmp/kt3 && timeout 400 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt3 -o bench -- python $REPO/bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-infer > "$OUT/trainpy_under_rocprof.log" 2>&1
+rm -rf "$TMPDIR/kt3" && timeout 400 rocprofv3 --kernel-trace --output-format csv -d "$TMPDIR/kt3" -o bench -- python $REPO/bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-infer > "$OUT/trainpy_under_rocprof.log" 2>&1
 echo "rocprof kernel-trace exit $?" >> "$OUT/trainpy_under_rocprof.log"
 TR=$(find /tmp/kt3 -name "*kernel_trace.csv" | head -1)
 grep '^{' "$OUT/trainpy_under_rocprof.log" | tail -1 > "$OUT/bench_line_under_rocprof.json"

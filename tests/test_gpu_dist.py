@@ -296,7 +296,7 @@ def test_bench_script_with_two_ranks_as_the_driver_launches_it():
     env = dict(os.environ, BENCH_SHARED_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--no-infer", "--no-cpu-baseline"]
+           "--full", "--no-infer", "--no-cpu-baseline"]            # --full: the per-kernel roofline leg asserted below
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=420, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -450,3 +450,14 @@ def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
     assert np.load(tmp_path / "a" / "loss.npy")[0] == 1.5
     z = np.load(tmp_path / "a" / "out0_z.npy")
     assert z.ndim == 1 and 0 < z.size <= bench.DUMP_MAX_ELEMS and np.isin(z, last["out"][0].numpy().reshape(-1)).all()
+
+
+def test_bench_has_the_full_option_off_by_default():
+    """bench.py --full, the option that carries every leg beside the headline, exists and is a plain flag (what a run without it
+    prints: tests/test_gpu_bench_path.py::test_bench_dump_outputs_are_the_same_in_two_runs)."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, PYTHONNOUSERSITE="1"), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert re.search(r"\[--full\]", r.stdout), r.stdout[:1500]

@@ -179,6 +179,10 @@ SIGNATURES = {
     "ft_stft_pow2": ([_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "ft_stft_pow2_ragged": ([_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p], _i),
     "ft_istft_pow2": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
+    "ft_stft_r8_ragged_phase": ([_p, _p, _p, _p, _p, _i, _i, _i, _p], _i),
+    "ft_istft_r8_ragged": ([_p, _p, _p, _p, _p, _i, _i, _i, _p], _i),
+    "ft_stft_pow2_ragged_phase": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
+    "ft_istft_pow2_ragged": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "ft_attn_ctc_workspace_floats": ([_i, _i, _i], _sz),
     "ft_attn_ctc_fwd": ([_p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _p], _i),
     "ft_attn_ctc_bwd": ([_p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _p], _i),

@@ -5,7 +5,9 @@ in LDS + |X| + mel filterbank + log-compression) instead of a 1026x1024 dense-DF
 The synthesis side (audio_processing.py:7-75, 237-270) is here too: STFT.inverse / STFT.forward run
 the inverse real FFT + overlap-add kernel ft_istft_r8, `griffin_lim` loops it with ft_stft_r8 on the
 device, and `window_sumsquare` is the reference's host function.  TacotronSTFT.mel_to_magnitude /
-mel_to_audio (not in the reference) turn model output into a waveform.
+mel_to_audio (not in the reference) turn model output into a waveform; the `_ragged` forms (STFT.transform_ragged /
+inverse_ragged, `griffin_lim_ragged`, mel_to_magnitude_ragged / mel_to_audio_ragged) do the same for a batch of utterances of
+different lengths in one launch per step.
 
 The mel filterbank constants come from librosa in the reference (third-party dependency that is
 not vendored: requirements.txt:4 pins 0.6.3, Dockerfile:6 pins 0.8.0; call site
@@ -113,6 +115,80 @@ def griffin_lim(magnitudes, stft_fn, n_iters=30):
     return signal
 
 
+def _host_lengths(lengths, B, lo, hi, name, rule):
+    """The per-utterance lengths of a ragged batch as a list of B Python ints in lo ..= hi: a list, a tuple or a CPU integer
+    tensor (what Flowtron.infer(..., return_lengths=True) hands back).  ValueError names the argument and the utterance."""
+    if torch.is_tensor(lengths):
+        if lengths.is_cuda or lengths.dim() != 1 or lengths.is_floating_point() or lengths.is_complex() \
+                or lengths.dtype == torch.bool:
+            raise ValueError("%s must be host integers (a list, a tuple or a 1-D CPU integer tensor), got a %s %s tensor of shape %s"
+                             % (name, lengths.device.type, lengths.dtype, tuple(lengths.shape)))
+        lengths = lengths.tolist()
+    elif isinstance(lengths, np.ndarray):
+        lengths = lengths.tolist()
+    elif not isinstance(lengths, (list, tuple)):
+        raise ValueError("%s must be host integers (a list, a tuple or a 1-D CPU integer tensor), got %s"
+                         % (name, type(lengths).__name__))
+    if len(lengths) != B:
+        raise ValueError("%s holds %d lengths for a batch of %d utterances" % (name, len(lengths), B))
+    out = []
+    for b, n in enumerate(lengths):
+        if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)):
+            raise ValueError("%s[%d] = %r is not an integer" % (name, b, n))
+        if not lo <= n <= hi:
+            raise ValueError("%s[%d] = %d is outside %s" % (name, b, n, rule))
+        out.append(int(n))
+    return out
+
+
+def _check_reflect(lens, stft_fn, what, name):
+    """griffin_lim's rule for every utterance of a ragged batch: its own samples must outnumber the reflect padding."""
+    for b, n in enumerate(lens):
+        if stft_fn.hop_length * (n - 1) <= stft_fn.filter_length // 2:
+            raise ValueError("%s needs hop * (%s[b] - 1) > filter_length / 2 samples for the reflect padding of STFT.transform; "
+                             "got %s[%d] = %d frames at hop %d" % (what, name, name, b, n, stft_fn.hop_length))
+
+
+def _lengths_to_device(values, device):
+    """Host ints -> int32 on the device through pinned memory, without blocking the host (as Flowtron.infer_batch does)."""
+    return torch.tensor(values, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
+
+
+def griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters=30, angles=None):
+    """griffin_lim for a batch of utterances of different lengths in one pass: magnitudes [B, n_fft/2+1, T] (device tensor),
+    utterance b holds n_frames[b] <= T frames (host integers); frames behind that may hold anything, they are never read.
+    Returns [B, hop * (T - 1)]: utterance b occupies [: hop * (n_frames[b] - 1)] and equals griffin_lim on its own frames from
+    the same starting angles, zeros behind.  angles=None draws np.random.rand(*magnitudes.size()) exactly as griffin_lim does
+    (with every length = T the two start from the same point under one seed); otherwise a [B, n_fft/2+1, T] starting phase on
+    the host or the device.  The lengths go to the device once; then 1 + 2 n_iters launches (ft_istft_*_ragged, and
+    ft_stft_*_ragged_phase storing the phase only) serve the whole batch without a host synchronisation."""
+    L.require_cuda(magnitudes)
+    stft_fn._check_spectrum(magnitudes, magnitudes)
+    B, nb, T = magnitudes.shape
+    hop = stft_fn.hop_length
+    lens = _host_lengths(n_frames, B, 1, T, "n_frames", "1 ..= T = %d" % T)
+    _check_reflect(lens, stft_fn, "griffin_lim_ragged", "n_frames")
+    if angles is None:
+        angles = np.angle(np.exp(2j * np.pi * np.random.rand(*magnitudes.size())))
+        angles = torch.from_numpy(angles.astype(np.float32))
+    else:
+        angles = torch.as_tensor(angles)
+        if tuple(angles.shape) != (B, nb, T):
+            raise ValueError("griffin_lim_ragged needs angles of the magnitudes' shape %s, got %s"
+                             % ((B, nb, T), tuple(angles.shape)))
+    angles = angles.to(magnitudes.device, torch.float32).contiguous()
+    m = magnitudes.contiguous().float()
+    if stft_fn.fft_window.device != m.device:
+        stft_fn.to(m.device)
+    both = _lengths_to_device(lens + [hop * (n - 1) for n in lens], m.device)
+    nf, ns = both[:B], both[B:]
+    signal = stft_fn._inverse_ragged(m, angles, nf)
+    for _ in range(n_iters):
+        _, angles = stft_fn._transform_ragged(signal, ns, want_magnitude=False)
+        signal = stft_fn._inverse_ragged(m, angles, nf)
+    return signal
+
+
 def dynamic_range_compression(x, C=1, clip_val=1e-5):
     return torch.log(torch.clamp(x, min=clip_val) * C)
 
@@ -212,6 +288,64 @@ class STFT(torch.nn.Module):
                                           self.hop_length, self.win_length, L.stream()), "ft_istft_pow2")
         return y
 
+    def _transform_ragged(self, y, ns, want_magnitude=True):
+        """y [B,N] contiguous fp32, ns [B] int32 on the device -> (magnitude or None, phase): one launch."""
+        B, N = y.shape
+        phase = torch.empty(B, self.filter_length // 2 + 1, N // self.hop_length + 1, device=y.device, dtype=torch.float32)
+        mag = torch.empty_like(phase) if want_magnitude else None
+        if self.fast_path():
+            L.check(L.lib().ft_stft_r8_ragged_phase(L.ptr(y), L.ptr(ns), L.ptr(self.fft_window), L.ptr(mag), L.ptr(phase), B, N,
+                                                    self.hop_length, L.stream()), "ft_stft_r8_ragged_phase")
+        else:
+            L.check(L.lib().ft_stft_pow2_ragged_phase(L.ptr(y), L.ptr(ns), L.ptr(self.fft_window), L.ptr(mag), L.ptr(phase), B, N,
+                                                      self.filter_length, self.hop_length, self.win_length, L.stream()),
+                    "ft_stft_pow2_ragged_phase")
+        return mag, phase
+
+    def transform_ragged(self, input_data, n_samples):
+        """transform for a zero-padded batch in one launch (ft_stft_r8_ragged_phase / ft_stft_pow2_ragged_phase): y [B,N] on the
+        device, utterance b holds n_samples[b] samples (host integers, n_fft/2 < n <= N) -> (magnitude, phase), each
+        [B, n_fft/2+1, N // hop + 1]: frames t < n_samples[b] // hop + 1 equal transform(y[b:b+1, :n_samples[b]]) (the reflect
+        padding is about the utterance's own end, the samples behind it are never read), later frames are zero."""
+        L.require_cuda(input_data)
+        self._require_device_path("STFT.transform_ragged")
+        if input_data.dim() != 2:
+            raise ValueError("STFT.transform_ragged needs y of shape [B, N], got %s" % (tuple(input_data.shape),))
+        y = input_data.contiguous().float()
+        B, N = y.shape
+        half = self.filter_length // 2
+        lens = _host_lengths(n_samples, B, half + 1, N, "n_samples", "filter_length / 2 = %d < n <= N = %d" % (half, N))
+        if self.fft_window.device != y.device:
+            self.to(y.device)
+        return self._transform_ragged(y, _lengths_to_device(lens, y.device))
+
+    def _inverse_ragged(self, m, ph, nf):
+        """m, ph [B, n_fft/2+1, T] contiguous fp32, nf [B] int32 on the device -> [B, hop * (T - 1)]: one launch."""
+        B, _, T = m.shape
+        y = torch.empty(B, self.hop_length * max(T - 1, 0), device=m.device, dtype=torch.float32)
+        if T >= 2 and self.fast_path():                 # one frame leaves nothing after the two n_fft/2-sample trims
+            L.check(L.lib().ft_istft_r8_ragged(L.ptr(m), L.ptr(ph), L.ptr(nf), L.ptr(self.fft_window), L.ptr(y), B, T,
+                                               self.hop_length, L.stream()), "ft_istft_r8_ragged")
+        elif T >= 2:
+            L.check(L.lib().ft_istft_pow2_ragged(L.ptr(m), L.ptr(ph), L.ptr(nf), L.ptr(self.fft_window), L.ptr(y), B, T,
+                                                 self.filter_length, self.hop_length, self.win_length, L.stream()),
+                    "ft_istft_pow2_ragged")
+        return y
+
+    def inverse_ragged(self, magnitude, phase, n_frames):
+        """inverse for a batch of utterances of different lengths in one launch (ft_istft_r8_ragged / ft_istft_pow2_ragged):
+        [B, n_fft/2+1, T] x 2 on the device, utterance b holds n_frames[b] frames (host integers, 1 ..= T) ->
+        [B, 1, hop * (T - 1)]: the samples [: hop * (n_frames[b] - 1)] equal inverse(magnitude[b:b+1, :, :n_frames[b]], ...),
+        zeros behind; the frames t >= n_frames[b] are never read."""
+        L.require_cuda(magnitude, phase)
+        self._check_spectrum(magnitude, phase)
+        m, ph = magnitude.contiguous().float(), phase.contiguous().float()
+        B, _, T = m.shape
+        lens = _host_lengths(n_frames, B, 1, T, "n_frames", "1 ..= T = %d" % T)
+        if self.fft_window.device != m.device:
+            self.to(m.device)
+        return self._inverse_ragged(m, ph, _lengths_to_device(lens, m.device)).unsqueeze(1)
+
     def forward(self, input_data):
         """audio_processing.py:265-268."""
         self.magnitude, self.phase = self.transform(input_data)
@@ -305,7 +439,7 @@ class TacotronSTFT(torch.nn.Module):
         """Addition, not in the reference: log-mel [B, n_mel, T] (or [n_mel, T]) -> linear magnitudes [B, n_fft/2+1, T]
         (or [n_fft/2+1, T]) = relu(pinv(mel_basis) @ spectral_de_normalize(mel)), the product on ft_gemm in fp32 with the
         ReLU epilogue, one batched call.  Frames after an utterance's end that hold zeros decode as magnitude 1, not
-        silence: trim each utterance to its own length first (ragged batches are not supported)."""
+        silence: a batch of different lengths goes to mel_to_magnitude_ragged."""
         L.require_cuda(mel)
         if mel.dim() not in (2, 3) or mel.shape[-2] != self.n_mel_channels:
             raise ValueError("mel_to_magnitude needs [B, %d, T] or [%d, T], got %s"
@@ -324,8 +458,35 @@ class TacotronSTFT(torch.nn.Module):
     def mel_to_audio(self, mel, n_iters=30):
         """Addition, not in the reference: log-mel [B, n_mel, T] (a dense batch, e.g. Flowtron.infer's output) or [n_mel, T]
         -> waveform [B, hop * (T - 1)] (or [hop * (T - 1)]) = griffin_lim(mel_to_magnitude(mel), self.stft_fn, n_iters).
-        Every utterance of a batch must fill all T frames: trim padded or post-stop frames before vocoding (zeros decode as
-        magnitude 1, not silence)."""
+        Every utterance of a batch must fill all T frames (zeros decode as magnitude 1, not silence): a batch of different
+        lengths, such as Flowtron.infer(..., return_lengths=True) returns, goes to mel_to_audio_ragged."""
         mag = self.mel_to_magnitude(mel)
         y = griffin_lim(mag if mag.dim() == 3 else mag[None], self.stft_fn, n_iters)
         return y if mel.dim() == 3 else y[0]
+
+    def _check_ragged_mel(self, mel, lengths, what):
+        L.require_cuda(mel)
+        if mel.dim() != 3 or mel.shape[1] != self.n_mel_channels:
+            raise ValueError("%s needs [B, %d, T], got %s" % (what, self.n_mel_channels, tuple(mel.shape)))
+        B, _, T = mel.shape
+        return _host_lengths(lengths, B, 1, T, "lengths", "1 ..= T = %d" % T)
+
+    def mel_to_magnitude_ragged(self, mel, lengths):
+        """mel_to_magnitude for a batch of different lengths: log-mel [B, n_mel, T], utterance b holds lengths[b] frames (host
+        integers) -> [B, n_fft/2+1, T] with mel_to_magnitude's values inside each utterance and zero behind it."""
+        lens = self._check_ragged_mel(mel, lengths, "mel_to_magnitude_ragged")
+        mag = self.mel_to_magnitude(mel)
+        T = mag.shape[2]
+        behind = torch.arange(T, device=mag.device)[None, None, :] >= _lengths_to_device(lens, mag.device)[:, None, None]
+        return mag.masked_fill_(behind, 0.0)
+
+    def mel_to_audio_ragged(self, mel, lengths, n_iters=30, angles=None):
+        """mel_to_audio for a batch of different lengths in one Griffin-Lim pass: log-mel [B, n_mel, T] and the frames each
+        utterance holds (host integers: Flowtron.infer(..., in_lens=, out_lens=, return_lengths=True) returns both) -> waveform
+        [B, hop * (T - 1)] = griffin_lim_ragged(mel_to_magnitude(mel), lengths, self.stft_fn, n_iters, angles): utterance b
+        occupies [: hop * (lengths[b] - 1)], zeros behind.  The frames behind an utterance's end are never read by the loop."""
+        L.require_cuda(mel)
+        self.stft_fn._require_device_path("TacotronSTFT.mel_to_audio_ragged")
+        lens = self._check_ragged_mel(mel, lengths, "mel_to_audio_ragged")
+        _check_reflect(lens, self.stft_fn, "mel_to_audio_ragged", "lengths")
+        return griffin_lim_ragged(self.mel_to_magnitude(mel), lens, self.stft_fn, n_iters, angles)

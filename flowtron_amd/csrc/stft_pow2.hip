@@ -129,7 +129,7 @@ struct StftP {
     const int* n_samples;            // ragged batch: utterance b holds n_samples[b] <= N samples and n_samples[b] / hop + 1
     int ldt;                         // frames; frames beyond that are written as zeros; ldt = output row stride
     int fpw;                         // frames per wave
-};
+};                                   // phase without mag (ft_stft_pow2_ragged_phase): the magnitude store is skipped
 
 // dynamic LDS of the forward kernel: tw [H+1] cpx | T [WAVES][H] cpx | mo [n_mel][FPG+1] | bw [BWMAX] | xs [span]
 size_t stft_lds_bytes(int n_fft, int hop, int n_mel, bool mel, int fpw) {
@@ -204,8 +204,8 @@ __global__ __launch_bounds__(256) void stft_pow2_k(StftP p) {
                 const cpx w = cmul(tw[k], mul_mi(o));                              // -i e^{-2 pi i k / N} o
                 const float re = e.re + w.re, im = e.im + w.im;
                 mk[r] = sqrtf(re * re + im * im);
-                if (p.mag) {
-                    p.mag[((size_t)b * (H + 1) + k) * p.ldt + t] = mk[r];
+                if (p.phase) {
+                    if (p.mag) p.mag[((size_t)b * (H + 1) + k) * p.ldt + t] = mk[r];
                     p.phase[((size_t)b * (H + 1) + k) * p.ldt + t] = atan2f(im, re);
                 }
             }
@@ -242,6 +242,14 @@ __global__ __launch_bounds__(256) void stft_pow2_k(StftP p) {
             lds_order();
         }
     }
+    if (p.phase && p.n_samples) {                                         // a ragged spectrum is zero behind the utterance's last frame
+        const int te = min(f0 + (wave + 1) * p.fpw, p.n_frames);
+        for (int t = max(f0 + wave * p.fpw, nfb); t < te; ++t)
+            for (int k = lane; k <= H; k += 64) {
+                if (p.mag) p.mag[((size_t)b * (H + 1) + k) * p.ldt + t] = 0.f;
+                p.phase[((size_t)b * (H + 1) + k) * p.ldt + t] = 0.f;
+            }
+    }
     if (p.mel) {                                                          // [band][FPG consecutive frames]
         __syncthreads();
         const int nf = min(FPG, p.n_frames - f0);
@@ -269,8 +277,9 @@ constexpr int SPT = 16, OWN = 256 * SPT;
 struct IstftP {
     const float* mag; const float* phase; const float* window;
     float* y;
-    int T, hop, n_out;
-};
+    int T, hop, n_out;               // T: frames per spectrum row (the row stride), n_out = hop (T - 1): samples per output row
+    const int* n_frames;             // ragged batch (ft_istft_pow2_ragged): utterance b holds n_frames[b] <= T frames; later frames are
+};                                   // never read and the samples from hop (n_frames[b] - 1) on are written as zeros
 
 // dynamic LDS of the inverse kernel: tw [H+1] cpx | X [WAVES][H+1] cpx | wl [N]
 size_t istft_lds_bytes(int n_fft) {
@@ -286,9 +295,16 @@ __global__ __launch_bounds__(256) void istft_pow2_k(IstftP p) {
     cpx* tr = tw + (H + 1);
     float* wl = reinterpret_cast<float*>(tr + WAVES * (H + 1));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.y, hop = p.hop, T = p.T;
+    const int b = blockIdx.y, hop = p.hop, ldt = p.T;
+    const int T = p.n_frames ? min(max(p.n_frames[b], 1), ldt) : ldt;    // this utterance's own frame count (uniform: SGPRs)
     const int n0 = blockIdx.x * OWN;
-    const int u0 = n0 + H, u1 = min(n0 + OWN, p.n_out) + H;               // untrimmed sample range [u0, u1) of this workgroup
+    const int nz1 = min(n0 + OWN, p.n_out);                               // the workgroup stores [n0, nz1): zeros from hop (T - 1) on
+    float* yb = p.y + (size_t)b * p.n_out;
+    if (n0 >= hop * (T - 1)) {                                            // wholly behind the utterance's end (ragged batch only)
+        for (int n = n0 + tid; n < nz1; n += 256) yb[n] = 0.f;
+        return;
+    }
+    const int u0 = n0 + H, u1 = min(n0 + OWN, hop * (T - 1)) + H;         // untrimmed sample range [u0, u1) of this workgroup
     const int t_lo = u0 - (N - 1) <= 0 ? 0 : (u0 - (N - 1) + hop - 1) / hop;
     const int t_hi = min(T - 1, (u1 - 1) / hop);                          // frames t_lo .. t_hi cover [u0, u1)
     fill_twiddles<H>(tw, tid);
@@ -298,8 +314,8 @@ __global__ __launch_bounds__(256) void istft_pow2_k(IstftP p) {
 #pragma unroll
     for (int i = 0; i < SPT; ++i) acc[i] = wss[i] = 0.f;
     cpx* X = tr + wave * (H + 1);
-    const float* magb = p.mag + (size_t)b * (H + 1) * T;
-    const float* phb = p.phase + (size_t)b * (H + 1) * T;
+    const float* magb = p.mag + (size_t)b * (H + 1) * ldt;
+    const float* phb = p.phase + (size_t)b * (H + 1) * ldt;
     for (int c0 = t_lo; c0 <= t_hi; c0 += WAVES) {
         const int t = c0 + wave;
         if (t <= t_hi) {                                                  // wave-uniform
@@ -308,7 +324,7 @@ __global__ __launch_bounds__(256) void istft_pow2_k(IstftP p) {
 #pragma unroll
             for (int j = 0; j <= PL; ++j) {
                 const int k = lane + 64 * j;
-                if (k <= H) X[k] = (cpx){magb[(size_t)k * T + t], phb[(size_t)k * T + t]};
+                if (k <= H) X[k] = (cpx){magb[(size_t)k * ldt + t], phb[(size_t)k * ldt + t]};
             }
             lds_order();
 #pragma unroll 1
@@ -364,11 +380,11 @@ __global__ __launch_bounds__(256) void istft_pow2_k(IstftP p) {
         __syncthreads();
     }
     // ---- divide by the window's sum-square envelope where it is > FLT_MIN (the reference's tiny(float32) rule), store
-    float* yb = p.y + (size_t)b * p.n_out;
 #pragma unroll
     for (int i = 0; i < SPT; ++i) {
         const int u = u0 + tid + 256 * i;
         if (u < u1) yb[u - H] = wss[i] > FLT_MIN ? acc[i] / wss[i] : acc[i];
+        else if (u - H < nz1) yb[u - H] = 0.f;                            // behind the utterance's end (ragged batch only)
     }
 }
 
@@ -414,6 +430,17 @@ int launch_istft(const IstftP& p, int B, hipStream_t s) {
     return FT_OK;
 }
 
+int istft_dispatch(const IstftP& p, int B, int n_fft, void* stream) {
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    switch (log2_pow2_nfft(n_fft)) {
+        case 8: return launch_istft<7>(p, B, s);
+        case 9: return launch_istft<8>(p, B, s);
+        case 10: return launch_istft<9>(p, B, s);
+        case 11: return launch_istft<10>(p, B, s);
+        default: return launch_istft<11>(p, B, s);
+    }
+}
+
 }  // namespace
 
 // y [B,N] -> any of mel [B,n_mel,T] (needs the CSR filterbank), mag [B,n_fft/2+1,T], phase [B,n_fft/2+1,T] (both or neither);
@@ -445,6 +472,20 @@ extern "C" int ft_stft_pow2_ragged(const float* y, const int32_t* n_samples, con
     return stft_dispatch(p, B, n_fft, stream);
 }
 
+// The spectrum of a ragged batch, as ft_stft_r8_ragged_phase: y [B,N], utterance b holds n_samples[b] samples (device int32) ->
+// mag (NULL = skip the store) and phase [B,n_fft/2+1,T_out], T_out = N / hop + 1: frames < n_samples[b] / hop + 1 exactly as
+// ft_stft_pow2 computes them for y[b, :n_samples[b]] alone (reflection about ITS last sample), zeros beyond in every output
+// that is written.  Same preconditions as ft_stft_pow2.
+extern "C" int ft_stft_pow2_ragged_phase(const float* y, const int32_t* n_samples, const float* window, float* mag, float* phase,
+                                         int B, int N, int n_fft, int hop, int win_length, void* stream) {
+    FT_CHECK_ARG(y && n_samples && window && phase);
+    FT_CHECK_ARG(log2_pow2_nfft(n_fft) > 0 && hop >= 1 && hop <= win_length && win_length <= n_fft);
+    FT_CHECK_ARG(B >= 1 && B <= 65535 && N > n_fft / 2);
+    const int n_frames = N / hop + 1;
+    StftP p{y, window, nullptr, nullptr, nullptr, nullptr, mag, phase, N, hop, 0, n_frames, n_samples, n_frames, 1};
+    return stft_dispatch(p, B, n_fft, stream);
+}
+
 // (mag, phase) [B,n_fft/2+1,T] -> y [B, hop (T-1)]: STFT.inverse (audio_processing.py:237-263) for n_fft = 256 .. 4096 (a power
 // of two), 1 <= hop <= win_length <= n_fft; window: hann [n_fft] (win_length zero-padded by the caller), as ft_stft_pow2.
 extern "C" int ft_istft_pow2(const float* mag, const float* phase, const float* window, float* y, int B, int T, int n_fft,
@@ -454,13 +495,19 @@ extern "C" int ft_istft_pow2(const float* mag, const float* phase, const float* 
     FT_CHECK_ARG(B >= 1 && B <= 65535 && T >= 2);
     FT_CHECK_ARG((int64_t)hop * (T - 1) <= INT32_MAX - 2 * n_fft - OWN);
     const int n_out = hop * (T - 1);
-    IstftP p{mag, phase, window, y, T, hop, n_out};
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (log2_pow2_nfft(n_fft)) {
-        case 8: return launch_istft<7>(p, B, s);
-        case 9: return launch_istft<8>(p, B, s);
-        case 10: return launch_istft<9>(p, B, s);
-        case 11: return launch_istft<10>(p, B, s);
-        default: return launch_istft<11>(p, B, s);
-    }
+    return istft_dispatch(IstftP{mag, phase, window, y, T, hop, n_out, nullptr}, B, n_fft, stream);
+}
+
+// The inverse of a ragged batch, as ft_istft_r8_ragged: (mag, phase) [B,n_fft/2+1,T] with row stride T, utterance b holds
+// n_frames[b] frames (device int32, 1 <= n_frames[b] <= T) -> y [B, hop (T-1)]: the samples n < hop (n_frames[b] - 1) exactly as
+// ft_istft_pow2 computes them for mag[b, :, :n_frames[b]] alone, zeros behind; frames t >= n_frames[b] are never read.  ONE
+// launch for the batch, no atomics, launch-independent.  Same preconditions as ft_istft_pow2.
+extern "C" int ft_istft_pow2_ragged(const float* mag, const float* phase, const int32_t* n_frames, const float* window, float* y,
+                                    int B, int T, int n_fft, int hop, int win_length, void* stream) {
+    FT_CHECK_ARG(mag && phase && n_frames && window && y);
+    FT_CHECK_ARG(log2_pow2_nfft(n_fft) > 0 && hop >= 1 && hop <= win_length && win_length <= n_fft);
+    FT_CHECK_ARG(B >= 1 && B <= 65535 && T >= 2);
+    FT_CHECK_ARG((int64_t)hop * (T - 1) <= INT32_MAX - 2 * n_fft - OWN);
+    const int n_out = hop * (T - 1);
+    return istft_dispatch(IstftP{mag, phase, window, y, T, hop, n_out, n_frames}, B, n_fft, stream);
 }

@@ -100,7 +100,7 @@ struct StftP {
     int N, hop, n_mel, n_frames;
     const int* n_samples;            // ragged batch (ft_stft_r8_ragged): utterance b holds n_samples[b] <= N samples and
     int ldt;                         // n_samples[b] / hop + 1 frames; frames beyond that are written as zeros; ldt = output row stride
-};
+};                                   // phase without mag (ft_stft_r8_ragged_phase): the magnitude store is skipped
 
 __global__ __launch_bounds__(256) void stft_r8_k(StftP p) {
     __shared__ __attribute__((aligned(16))) float xs[SPAN];
@@ -197,8 +197,8 @@ __global__ __launch_bounds__(256) void stft_r8_k(StftP p) {
                 const float re = e.re + tw.re, im = e.im + tw.im;
                 const float m = sqrtf(re * re + im * im);
                 M[k] = m;
-                if (p.mag) {
-                    p.mag[((size_t)b * NB + k) * p.ldt + t] = m;
+                if (p.phase) {
+                    if (p.mag) p.mag[((size_t)b * NB + k) * p.ldt + t] = m;
                     p.phase[((size_t)b * NB + k) * p.ldt + t] = atan2f(im, re);
                 }
             }
@@ -231,6 +231,14 @@ __global__ __launch_bounds__(256) void stft_r8_k(StftP p) {
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    if (p.phase && p.n_samples) {                                         // a ragged spectrum is zero behind the utterance's last frame
+        const int te = min(f0 + (wave + 1) * FPW, p.n_frames);
+        for (int t = max(f0 + wave * FPW, nfb); t < te; ++t)
+            for (int k = lane; k <= NH; k += 64) {
+                if (p.mag) p.mag[((size_t)b * NB + k) * p.ldt + t] = 0.f;
+                p.phase[((size_t)b * NB + k) * p.ldt + t] = 0.f;
+            }
     }
     if (p.mel) {                                                          // [band][16 consecutive frames]: 64-byte row pieces
         __syncthreads();
@@ -275,6 +283,21 @@ extern "C" int ft_stft_r8_ragged(const float* y, const int32_t* n_samples, const
     return FT_OK;
 }
 
+// The spectrum of a ragged batch (the analysis step of griffin_lim_ragged): y [B,N], utterance b holds n_samples[b] samples
+// (device int32) -> mag (NULL = skip the store: Griffin-Lim keeps the phase only) and phase [B,513,T_out], T_out = N / hop + 1:
+// frames < n_samples[b] / hop + 1 exactly as ft_stft_r8 computes them for y[b, :n_samples[b]] alone (reflection about ITS last
+// sample, so the samples behind it are never read), zeros beyond in every output that is written.  ONE launch for the batch.
+extern "C" int ft_stft_r8_ragged_phase(const float* y, const int32_t* n_samples, const float* window, float* mag, float* phase,
+                                       int B, int N, int hop, void* stream) {
+    FT_CHECK_ARG(y && n_samples && window && phase);
+    FT_CHECK_ARG(B >= 1 && B <= 65535 && hop >= 1 && hop <= 256 && N > NH);
+    const int n_frames = N / hop + 1;
+    StftP p{y, window, nullptr, nullptr, nullptr, nullptr, mag, phase, N, hop, 0, n_frames, n_samples, n_frames};
+    hipLaunchKernelGGL(stft_r8_k, dim3(cdiv(n_frames, FPG), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
+    FT_CHECK_LAUNCH();
+    return FT_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------
 // Inverse STFT (audio_processing.py:237-263, STFT.inverse) for the same setting: (magnitude, phase) [B,513,T] -> y [B,hop*(T-1)],
 //
@@ -300,18 +323,26 @@ constexpr int SPT = 16;                                // owned samples per thre
 struct IstftP {
     const float* mag; const float* phase; const float* window;
     float* y;
-    int T, hop, n_out;
-};
+    int T, hop, n_out;               // T: frames per spectrum row (the row stride), n_out = hop (T - 1): samples per output row
+    const int* n_frames;             // ragged batch (ft_istft_r8_ragged): utterance b holds n_frames[b] <= T frames; later frames are
+};                                   // never read and the samples from hop (n_frames[b] - 1) on are written as zeros
 
 __global__ __launch_bounds__(256) void istft_r8_k(IstftP p) {
     __shared__ __attribute__((aligned(16))) float fr[FC][NFFT];          // windowed irfft of the round's frames
     __shared__ __attribute__((aligned(16))) cpx tr[4][NH + 1];           // per-wave spectrum / transpose buffer
     __shared__ float wl[NFFT];                                            // the window (for wss)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.y, hop = p.hop, T = p.T;
+    const int b = blockIdx.y, hop = p.hop, ldt = p.T;
+    const int T = p.n_frames ? min(max(p.n_frames[b], 1), ldt) : ldt;    // this utterance's own frame count (uniform: SGPRs)
     const int S = 16 * hop;
     const int n0 = blockIdx.x * S;
-    const int u0 = n0 + NH, u1 = min(n0 + S, p.n_out) + NH;              // untrimmed sample range [u0, u1) of this workgroup
+    const int nz1 = min(n0 + S, p.n_out);                                 // the workgroup stores [n0, nz1): zeros from hop (T - 1) on
+    float* yb = p.y + (size_t)b * p.n_out;
+    if (n0 >= hop * (T - 1)) {                                            // wholly behind the utterance's end (ragged batch only)
+        for (int n = n0 + tid; n < nz1; n += 256) yb[n] = 0.f;
+        return;
+    }
+    const int u0 = n0 + NH, u1 = min(n0 + S, hop * (T - 1)) + NH;        // untrimmed sample range [u0, u1) of this workgroup
     const int t_lo = u0 - (NFFT - 1) <= 0 ? 0 : (u0 - (NFFT - 1) + hop - 1) / hop;
     const int t_hi = min(T - 1, (u1 - 1) / hop);                          // frames t_lo .. t_hi cover [u0, u1)
     // per-lane constants: w1 = W512^{l k1}, w2 = W64^{b2 k2}, w3[j] = W1024^{k} of the lane's bins k = lane + 64 j, and the window
@@ -337,8 +368,8 @@ __global__ __launch_bounds__(256) void istft_r8_k(IstftP p) {
 #pragma unroll
     for (int i = 0; i < SPT; ++i) acc[i] = 0.f;
     cpx* X = tr[wave];
-    const float* magb = p.mag + (size_t)b * NB * T;
-    const float* phb = p.phase + (size_t)b * NB * T;
+    const float* magb = p.mag + (size_t)b * NB * ldt;
+    const float* phb = p.phase + (size_t)b * NB * ldt;
     for (int c0 = t_lo; c0 <= t_hi; c0 += FC) {
         for (int f = wave; f < FC; f += 4) {
             const int t = c0 + f;
@@ -348,10 +379,10 @@ __global__ __launch_bounds__(256) void istft_r8_k(IstftP p) {
             // sincosf (full range reduction, many registers) runs one bin at a time.
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const size_t o = (size_t)(lane + 64 * j) * T + t;
+                const size_t o = (size_t)(lane + 64 * j) * ldt + t;
                 X[lane + 64 * j] = (cpx){magb[o], phb[o]};
             }
-            if (lane == 0) X[NH] = (cpx){magb[(size_t)NH * T + t], phb[(size_t)NH * T + t]};
+            if (lane == 0) X[NH] = (cpx){magb[(size_t)NH * ldt + t], phb[(size_t)NH * ldt + t]};
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll 1
             for (int k = lane; k <= NH; k += 64) {
@@ -398,11 +429,12 @@ __global__ __launch_bounds__(256) void istft_r8_k(IstftP p) {
         __syncthreads();
     }
     // ---- divide by the window's sum-square envelope where it is > FLT_MIN (the reference's tiny(float32) rule), store
-    float* yb = p.y + (size_t)b * p.n_out;
 #pragma unroll
     for (int i = 0; i < SPT; ++i) {
         const int u = u0 + tid + 256 * i;
-        if (u < u1) {
+        if (u >= u1) {
+            if (u - NH < nz1) yb[u - NH] = 0.f;                           // behind the utterance's end (ragged batch only)
+        } else {
             const int ta = u - (NFFT - 1) <= 0 ? 0 : (u - (NFFT - 1) + hop - 1) / hop, tb = min(T - 1, u / hop);
             float wss = 0.f;
             for (int t = ta; t <= tb; ++t) {
@@ -424,7 +456,24 @@ extern "C" int ft_istft_r8(const float* mag, const float* phase, const float* wi
     FT_CHECK_ARG(B >= 1 && B <= 65535 && hop >= 1 && hop <= 256 && T >= 2);
     FT_CHECK_ARG((int64_t)hop * (T - 1) <= INT32_MAX - 2 * NFFT);
     const int n_out = hop * (T - 1);
-    IstftP p{mag, phase, window, y, T, hop, n_out};
+    IstftP p{mag, phase, window, y, T, hop, n_out, nullptr};
+    hipLaunchKernelGGL(istft_r8_k, dim3(cdiv(n_out, 16 * hop), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
+    FT_CHECK_LAUNCH();
+    return FT_OK;
+}
+
+// The inverse of a ragged batch (the synthesis step of griffin_lim_ragged): (mag, phase) [B,513,T] with row stride T, utterance b
+// holds n_frames[b] frames (device int32, 1 <= n_frames[b] <= T) -> y [B, hop (T-1)]: the samples n < hop (n_frames[b] - 1)
+// exactly as ft_istft_r8 computes them for mag[b, :, :n_frames[b]] alone (the covering frames, the wss sum and both 512-sample
+// trims use ITS frame count; the same ascending-t overlap-add and > FLT_MIN rule), zeros behind.  Frames t >= n_frames[b] are
+// never read.  ONE launch for the batch, no atomics, launch-independent.  Same preconditions as ft_istft_r8.
+extern "C" int ft_istft_r8_ragged(const float* mag, const float* phase, const int32_t* n_frames, const float* window, float* y,
+                                  int B, int T, int hop, void* stream) {
+    FT_CHECK_ARG(mag && phase && n_frames && window && y);
+    FT_CHECK_ARG(B >= 1 && B <= 65535 && hop >= 1 && hop <= 256 && T >= 2);
+    FT_CHECK_ARG((int64_t)hop * (T - 1) <= INT32_MAX - 2 * NFFT);
+    const int n_out = hop * (T - 1);
+    IstftP p{mag, phase, window, y, T, hop, n_out, n_frames};
     hipLaunchKernelGGL(istft_r8_k, dim3(cdiv(n_out, 16 * hop), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
     FT_CHECK_LAUNCH();
     return FT_OK;

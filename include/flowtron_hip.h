@@ -546,6 +546,19 @@ int ft_stft_r8_ragged(const float* y, const int32_t* n_samples, const float* win
  * the window's sum-square envelope where that is > FLT_MIN, first and last 512 samples cut.  Deterministic: no atomics, each
  * sample sums its frames in ascending t.  window: hann [1024] as ft_stft_r8.  T >= 2. */
 int ft_istft_r8(const float* mag, const float* phase, const float* window, float* y, int B, int T, int hop, void* stream);
+/* The synthesis side of a ragged batch (griffin_lim_ragged), ONE launch per batch each, on the kernels of the dense forms:
+ * ft_stft_r8_ragged_phase: y [B,N], utterance b holds n_samples[b] samples (device int32) -> mag (NULL = the magnitude store is
+ * skipped) and phase [B,513,N/hop+1]: frames t < n_samples[b] / hop + 1 exactly as ft_stft_r8 computes them for
+ * y[b, :n_samples[b]] alone (reflect padding about ITS last sample; later samples are never read), zeros beyond in every
+ * output that is written.
+ * ft_istft_r8_ragged: (mag, phase) [B,513,T] with row stride T, utterance b holds n_frames[b] frames (device int32,
+ * 1 <= n_frames[b] <= T) -> y [B, hop (T-1)]: samples n < hop (n_frames[b] - 1) exactly as ft_istft_r8 computes them for
+ * mag[b, :, :n_frames[b]] alone (covering frames, wss and both trims from ITS frame count), zeros behind; frames
+ * t >= n_frames[b] are never read.  No atomics, launch-independent.  Preconditions as the dense forms. */
+int ft_stft_r8_ragged_phase(const float* y, const int32_t* n_samples, const float* window, float* mag, float* phase, int B, int N,
+                            int hop, void* stream);
+int ft_istft_r8_ragged(const float* mag, const float* phase, const int32_t* n_frames, const float* window, float* y, int B, int T,
+                       int hop, void* stream);
 /* The same three for every power-of-two analysis size n_fft = 256 .. 4096 and any hop (csrc/stft_pow2.hip): an n_fft/2-point
  * complex FFT (Stockham, one radix-2 / -4 pass and radix-8 passes, one wave per frame) plus the split step.  Bins: n_fft/2+1.
  * 1 <= hop <= win_length <= n_fft; window: hann [n_fft] (win_length zero-padded by the caller); N > n_fft / 2.  Outputs, the
@@ -558,6 +571,12 @@ int ft_stft_pow2_ragged(const float* y, const int32_t* n_samples, const float* w
                         int n_mel, int T_out, void* stream);
 int ft_istft_pow2(const float* mag, const float* phase, const float* window, float* y, int B, int T, int n_fft, int hop,
                   int win_length, void* stream);
+/* ft_stft_r8_ragged_phase / ft_istft_r8_ragged for the power-of-two sizes: the same contracts against ft_stft_pow2 /
+ * ft_istft_pow2, bins n_fft/2+1, trims n_fft/2. */
+int ft_stft_pow2_ragged_phase(const float* y, const int32_t* n_samples, const float* window, float* mag, float* phase, int B,
+                              int N, int n_fft, int hop, int win_length, void* stream);
+int ft_istft_pow2_ragged(const float* mag, const float* phase, const int32_t* n_frames, const float* window, float* y, int B,
+                         int T, int n_fft, int hop, int win_length, void* stream);
 
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with

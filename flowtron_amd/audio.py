@@ -189,6 +189,126 @@ def griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters=30, angles=None):
     return signal
 
 
+RESAMPLE_WIDTH = 6           # zero crossings of the sinc kept on each side (the common torch audio library's lowpass_filter_width)
+RESAMPLE_RATES = (8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000)      # every ordered pair of these fits the kernel's table
+_RESAMPLE_HOST = {}          # (orig, new) -> (taps [new_g, K] fp32, phase_start [new_g] int32, orig_g, new_g, K)
+_RESAMPLE_DEV = {}           # (orig, new, device) -> (taps, phase_start) on the device
+
+
+def _check_rates(orig_sr, new_sr):
+    for name, r in (("orig_sr", orig_sr), ("new_sr", new_sr)):
+        if isinstance(r, (bool, np.bool_)) or not isinstance(r, (int, np.integer)) or r < 1:
+            raise ValueError("%s must be a positive integer number of Hz, got %r" % (name, r))
+    return int(orig_sr), int(new_sr)
+
+
+def resample_length(n, orig_sr, new_sr):
+    """Samples `resample` returns for n samples: ceil(n * new_sr / orig_sr), host integer arithmetic only."""
+    orig, new = _check_rates(orig_sr, new_sr)
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or n < 0:
+        raise ValueError("n must be a non-negative integer, got %r" % (n,))
+    return (int(n) * new + orig - 1) // orig
+
+
+def resample_taps(orig_sr, new_sr):
+    """The polyphase table of the Hann-windowed sinc (width RESAMPLE_WIDTH, rolloff 0.99) for orig_sr -> new_sr, built once per
+    pair in float64 and rounded to fp32: (taps [new_g, K], phase_start [new_g] int32, orig_g, new_g, K) with g = gcd,
+    orig_g = orig_sr / g, new_g = new_sr / g.  Output m = q new_g + p is sum_i taps[p, i] x[q orig_g + phase_start[p] + i], where
+    taps[p, i] = h((phase_start[p] + i) / orig_sr - p / new_sr), h(t) = (base / orig_sr) sinc(base t) cos^2(pi base t / (2 W))
+    inside |base t| < W, base = 0.99 min(orig_sr, new_sr).  The argument base t is formed from the exact integer
+    k new_sr - m orig_sr, so the table does not depend on which output of a phase it is evaluated at."""
+    orig, new = _check_rates(orig_sr, new_sr)
+    hit = _RESAMPLE_HOST.get((orig, new))
+    if hit is not None:
+        return hit
+    g = math.gcd(orig, new)
+    og, ng = orig // g, new // g
+    mn, W = min(orig, new), RESAMPLE_WIDTH
+    # |base t| < W  <=>  99 mn |num| < 100 W orig new  with  num = k new - m orig = g (j ng - p og),  j = k - q og
+    u_max = (100 * W * orig * new - 1) // (99 * mn * g)                  # largest |j ng - p og| inside the window
+    K = 2 * u_max // ng + 2                                              # no phase has more taps than this
+    if ng <= L.RESAMPLE_MAX_PHASES:
+        K = max((p * og + u_max) // ng + (u_max - p * og) // ng + 1 for p in range(ng))
+    if ng > L.RESAMPLE_MAX_PHASES or ng * K > L.RESAMPLE_MAX_TAPS:
+        raise NotImplementedError(
+            "resample %d -> %d Hz needs a table of %d phases x %d taps; the kernel holds at most %d phases and %d taps in all "
+            "(supported: every ordered pair of %s Hz, and any pair whose rates share a large enough common divisor)"
+            % (orig, new, ng, K, L.RESAMPLE_MAX_PHASES, L.RESAMPLE_MAX_TAPS, "/".join(map(str, RESAMPLE_RATES))))
+    taps = np.zeros((ng, K), dtype=np.float64)
+    start = np.zeros(ng, dtype=np.int32)
+    base = 0.99 * mn
+    for p in range(ng):
+        j_lo, j_hi = -((u_max - p * og) // ng), (p * og + u_max) // ng
+        start[p] = j_lo
+        for j in range(j_lo, j_hi + 1):
+            t = base * (g * (j * ng - p * og)) / (orig * new)
+            s = 1.0 if t == 0.0 else math.sin(math.pi * t) / (math.pi * t)
+            taps[p, j - j_lo] = (base / orig) * s * math.cos(math.pi * t / (2 * W)) ** 2
+    # the kernel sizes a tile's input span from these two facts (include/flowtron_hip.h)
+    assert np.all(np.diff(start) >= 0) and int(start[-1]) <= int(start[0]) + og
+    out = _RESAMPLE_HOST[(orig, new)] = (taps.astype(np.float32), start, og, ng, K)
+    return out
+
+
+def _resample_launch(x, ns_dev, orig, new, n_out_max):
+    """x [B, N] contiguous fp32 on the device, ns_dev int32 [B] on the device or None (every row N long) -> [B, n_out_max]:
+    one ft_resample_ragged launch."""
+    taps, start, og, ng, K = resample_taps(orig, new)
+    key = (orig, new, str(x.device))
+    dev = _RESAMPLE_DEV.get(key)
+    if dev is None:
+        dev = _RESAMPLE_DEV[key] = (torch.from_numpy(taps).to(x.device), torch.from_numpy(start).to(x.device))
+    B, N = x.shape
+    y = torch.empty(B, n_out_max, device=x.device, dtype=torch.float32)
+    L.check(L.lib().ft_resample_ragged(L.ptr(x), L.ptr(ns_dev), L.ptr(dev[0]), L.ptr(dev[1]), L.ptr(y), B, N, n_out_max, og, ng, K,
+                                       L.stream()), "ft_resample_ragged")
+    return y
+
+
+def resample(audio, orig_sr, new_sr):
+    """Bandlimited sample-rate conversion on the device (ft_resample_ragged, csrc/resample.hip): audio [N] or [B, N] at orig_sr
+    -> [n_out] or [B, n_out] at new_sr, n_out = resample_length(N, orig_sr, new_sr).  The filter is the Hann-windowed sinc the
+    common torch audio library uses at its defaults (lowpass_filter_width 6, rolloff 0.99); samples outside the signal count
+    as zero.  Equal rates return the input's values without a launch.  Rates: positive integers whose table fits the kernel
+    (every ordered pair of RESAMPLE_RATES does), NotImplementedError otherwise."""
+    orig, new = _check_rates(orig_sr, new_sr)
+    if not torch.is_tensor(audio) or audio.dim() not in (1, 2) or audio.shape[-1] < 1:
+        raise ValueError("resample needs audio of shape [N] or [B, N] with N >= 1, got %s"
+                         % (tuple(audio.shape) if torch.is_tensor(audio) else type(audio).__name__,))
+    if orig != new:
+        resample_taps(orig, new)
+    L.require_cuda(audio)
+    x = audio.contiguous().float()
+    if orig == new:
+        return x
+    x2 = x if x.dim() == 2 else x[None]
+    y = _resample_launch(x2, None, orig, new, resample_length(x2.shape[1], orig, new))
+    return y if x.dim() == 2 else y[0]
+
+
+def resample_ragged(audio, n_samples, orig_sr, new_sr):
+    """resample for a zero-padded batch of utterances of different lengths in one launch: audio [B, N] on the device, utterance b
+    holds n_samples[b] samples (host integers, 1 ..= N; the samples behind them are never read) -> (out [B, max_b n_out[b]],
+    n_out int64 CPU [B]) with n_out[b] = resample_length(n_samples[b], orig_sr, new_sr): out[b, :n_out[b]] equals
+    resample(audio[b, :n_samples[b]], ...) bit for bit, zeros behind."""
+    orig, new = _check_rates(orig_sr, new_sr)
+    if not torch.is_tensor(audio) or audio.dim() != 2 or audio.shape[1] < 1:
+        raise ValueError("resample_ragged needs audio of shape [B, N] with N >= 1, got %s"
+                         % (tuple(audio.shape) if torch.is_tensor(audio) else type(audio).__name__,))
+    B, N = audio.shape
+    lens = _host_lengths(n_samples, B, 1, N, "n_samples", "1 ..= N = %d" % N)
+    if orig != new:
+        resample_taps(orig, new)
+    L.require_cuda(audio)
+    x = audio.contiguous().float()
+    n_out = [resample_length(n, orig, new) for n in lens]
+    if orig == new:
+        behind = torch.arange(N, device=x.device)[None, :] >= _lengths_to_device(lens, x.device)[:, None]
+        return x.masked_fill(behind, 0.0)[:, :max(lens)], torch.tensor(n_out, dtype=torch.int64)
+    y = _resample_launch(x, _lengths_to_device(lens, x.device), orig, new, max(n_out))
+    return y, torch.tensor(n_out, dtype=torch.int64)
+
+
 def dynamic_range_compression(x, C=1, clip_val=1e-5):
     return torch.log(torch.clamp(x, min=clip_val) * C)
 

@@ -32,10 +32,13 @@ class DeferredMel:
     (train.py:286) -- the one call the reference makes on it.  Result: [B, n_mel, T_max] fp32 on the device, zero beyond
     each utterance's frames, exactly what DataCollate's zero padding produces (data.py:215-229)."""
 
-    def __init__(self, audio, n_samples, stft_args, max_t=None):
+    def __init__(self, audio, n_samples, stft_args, max_t=None, source_rates=None):
         # max_t: the padded frame count DataCollate uses for every slot of the batch (rounded up to a multiple of
         # n_frames_per_step, data.py:213-216); None = the longest utterance's own frame count
+        # source_rates: the sample rate of every row's audio (Data(resample=True)); rows at another rate than
+        # stft_args["sampling_rate"] are resampled on the device before the front end.  None = every row at the target rate
         self.audio, self.n_samples, self.stft_args, self.max_t = audio, n_samples, dict(stft_args), max_t
+        self.source_rates = None if source_rates is None else [int(r) for r in source_rates]
 
     def __len__(self):
         return self.audio.shape[0]
@@ -52,20 +55,42 @@ class DeferredMel:
         # batch -- measured at ~10 s per batch in a long-lived process with a large address space (a -m gpu suite run: 170 s
         # per training-loop test against 13 s in a fresh process).  A host memcpy into pinned memory + a DMA costs nothing.
         audio = _pinned_stage(self.audio).to(dev, non_blocking=False)
+        audio, n_samples = self._to_target_rate(audio, stft.sampling_rate)
         hop = stft.stft_fn.hop_length
-        frames = [int(n) // hop + 1 for n in self.n_samples.tolist()]
+        frames = [int(n) // hop + 1 for n in n_samples.tolist()]
         max_t = max(frames) if self.max_t is None else max(int(self.max_t), max(frames))
-        if stft.ragged_path() and int(self.n_samples.min()) > stft.stft_fn.filter_length // 2:
+        if stft.ragged_path() and int(n_samples.min()) > stft.stft_fn.filter_length // 2:
             # ONE launch for the batch: every utterance reflected about its own last sample, zeros behind its last frame.
             # Same preconditions as TacotronSTFT.mel_spectrogram's rFFT kernels: more than 128 mel channels, an
             # analysis setting outside fast_path() / pow2_path(), or an utterance no longer than the reflection pad (the
             # reference's reflect pad raises on those), take the per-utterance loop below, whose mel_spectrogram falls back to
             # the general front end (ft_stft_mel)
-            return stft.mel_spectrogram_ragged(audio, self.n_samples.to(dev, dtype=torch.int32), max_t)
+            return stft.mel_spectrogram_ragged(audio, n_samples.to(dev, dtype=torch.int32), max_t)
         mel = torch.zeros(len(frames), stft.n_mel_channels, max_t, device=dev, dtype=torch.float32)
-        for i, (n, t) in enumerate(zip(self.n_samples.tolist(), frames)):       # reflect padding depends on each utterance's end
+        for i, (n, t) in enumerate(zip(n_samples.tolist(), frames)):       # reflect padding depends on each utterance's end
             mel[i, :, :t] = stft.mel_spectrogram(audio[i:i + 1, :int(n)])[0]
         return mel
+
+    def _to_target_rate(self, audio, target):
+        """audio [B, N] on the device, row b holding n_samples[b] samples at source_rates[b] -> (audio [B, N'], n_samples [B] CPU)
+        at `target`: one ft_resample_ragged launch per distinct source rate other than the target; rows already at the target
+        rate are copied, not filtered."""
+        rates = self.source_rates
+        if rates is None or all(r == target for r in rates):
+            return audio, self.n_samples
+        from .audio import resample_length, resample_ragged
+        lens = self.n_samples.tolist()
+        new_lens = [n if r == target else resample_length(n, r, target) for n, r in zip(lens, rates)]
+        out = torch.zeros(len(lens), max(new_lens), device=audio.device, dtype=torch.float32)
+        for rate in sorted(set(rates)):
+            rows = [i for i, r in enumerate(rates) if r == rate]
+            idx = torch.tensor(rows, device=audio.device)
+            w = max(lens[i] for i in rows)
+            sub = audio.index_select(0, idx)[:, :w]
+            if rate != target:
+                sub, _ = resample_ragged(sub, [lens[i] for i in rows], rate, target)
+            out[:, :sub.shape[1]].index_copy_(0, idx, sub)
+        return out, torch.tensor(new_lens, dtype=torch.long)
 
     def to(self, device, non_blocking=False):
         return self.cuda(device, non_blocking)
@@ -108,10 +133,13 @@ def _pinned_stage(t):
 
 class AudioItem:
     """What `Data.__getitem__` puts in the mel slot of an item: normalised audio + the frame count DataCollate needs."""
-    __slots__ = ("audio", "n_frames", "stft_args", "prior_args")
+    __slots__ = ("audio", "n_frames", "stft_args", "prior_args", "source_rate")
 
-    def __init__(self, audio, n_frames, stft_args, prior_args=None):
+    def __init__(self, audio, n_frames, stft_args, prior_args=None, source_rate=None):
+        # source_rate: the rate the audio is at when it is not stft_args["sampling_rate"] (Data(resample=True)); n_frames then
+        # counts the frames of the audio AFTER the device resamples it
         self.audio, self.n_frames, self.stft_args, self.prior_args = audio, n_frames, stft_args, prior_args
+        self.source_rate = source_rate
 
     def size(self, dim):            # DataCollate reads x[0].size(0) = n_mel and x[0].size(1) = frames (data.py:211-212)
         return self.stft_args["n_mel_channels"] if dim == 0 else self.n_frames
@@ -138,13 +166,16 @@ class Data(torch.utils.data.Dataset):
     MI355X-side change: items carry normalised AUDIO (AudioItem); the mel spectrogram and the attention prior are computed on
     the device, per batch, after collate (DeferredMel / DeferredPrior) -- the DataLoader worker only reads files and runs
     the text front end.  The text front end itself (cleaners, CMUdict, ARPAbet; data.py:28, 164-171) is outside the hot path:
-    the reference's `text` package is used when it is importable, otherwise `text_frontend` must be given."""
+    the reference's `text` package is used when it is importable, otherwise `text_frontend` must be given.
+    `resample=True` (an addition, off by default) accepts files at another rate than `sampling_rate`: their audio travels at the
+    file's rate and is resampled on the device when the batch's mel slot goes to it (DeferredMel)."""
 
     def __init__(self, filelist_path, filter_length, hop_length, win_length, sampling_rate, mel_fmin, mel_fmax, max_wav_value,
                  p_arpabet, cmudict_path, text_cleaners, speaker_ids=None, use_attn_prior=False, attn_prior_threshold=1e-4,
                  prior_cache_path="", betab_scaling_factor=1.0, randomize=True, keep_ambiguous=False, seed=1234,
-                 text_frontend=None):
+                 text_frontend=None, resample=False):
         self.max_wav_value = max_wav_value
+        self.resample = bool(resample)
         self.audiopaths_and_text = load_filepaths_and_text(filelist_path)
         self.use_attn_prior = use_attn_prior
         self.betab_scaling_factor = betab_scaling_factor
@@ -203,11 +234,18 @@ class Data(torch.utils.data.Dataset):
     def __getitem__(self, index):
         audiopath, text, speaker_id = self.audiopaths_and_text[index]
         audio, sampling_rate = load_wav_to_torch(audiopath)
+        source_rate, n = None, audio.numel()
         if sampling_rate != self.sampling_rate:
-            raise ValueError("{} SR doesn't match target {} SR".format(sampling_rate, self.sampling_rate))
+            if not self.resample:
+                raise ValueError("{} SR doesn't match target {} SR".format(sampling_rate, self.sampling_rate))
+            from .audio import resample_length, resample_taps
+            source_rate = int(sampling_rate)
+            resample_taps(source_rate, self.sampling_rate)          # a pair the kernel does not take is refused here, on the host
+            n = resample_length(n, source_rate, self.sampling_rate)
         audio = audio / self.max_wav_value
-        item = AudioItem(audio, audio.numel() // self.hop_length + 1, self.stft_args,
-                         (self.betab_scaling_factor, self.attn_prior_threshold))     # train.py:69 builds DataCollate without them
+        item = AudioItem(audio, n // self.hop_length + 1, self.stft_args,
+                         (self.betab_scaling_factor, self.attn_prior_threshold),     # train.py:69 builds DataCollate without them
+                         source_rate)
         return (item, self.get_speaker_id(speaker_id), self.get_text(text), None)
 
     def __len__(self):
@@ -282,15 +320,19 @@ class DataCollate:
         gate_padded = torch.zeros(B, max_t, dtype=torch.float32)
         output_lengths = torch.zeros(B, dtype=torch.long)
         speaker_ids = torch.zeros(B, dtype=torch.long)
+        target = batch[0][0].stft_args["sampling_rate"]
+        source_rates = [target] * B
         for i, j in enumerate(order.tolist()):
             it, spk, text = batch[j][0], batch[j][1], batch[j][2]
             text_padded[i, :text.size(0)] = text
             audio[i, :it.audio.numel()] = it.audio
+            source_rates[i] = target if it.source_rate is None else it.source_rate
             n_samples[i] = it.audio.numel()
             gate_padded[i, it.n_frames - 1:] = 1
             output_lengths[i] = it.n_frames
             speaker_ids[i] = int(spk)
-        mel = DeferredMel(audio, n_samples, batch[0][0].stft_args, max_t=max_t)
+        mel = DeferredMel(audio, n_samples, batch[0][0].stft_args, max_t=max_t,
+                          source_rates=source_rates if any(r != target for r in source_rates) else None)
         scaling, thr = batch[0][0].prior_args or (self.betab_scaling_factor, self.attn_prior_threshold)
         prior = DeferredPrior(input_lengths, output_lengths, max_t, max_in, scaling, thr) if self.use_attn_prior else None
         return (mel, speaker_ids, text_padded, input_lengths, output_lengths, gate_padded, prior)

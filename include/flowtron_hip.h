@@ -578,6 +578,24 @@ int ft_stft_pow2_ragged_phase(const float* y, const int32_t* n_samples, const fl
 int ft_istft_pow2_ragged(const float* mag, const float* phase, const int32_t* n_frames, const float* window, float* y, int B,
                          int T, int n_fft, int hop, int win_length, void* stream);
 
+/* ---- sample-rate conversion (csrc/resample.hip; additive, not in the reference) ----------------------
+ * x [B,N] at `orig` Hz -> y [B,N_out] at `new` Hz by the Hann-windowed sinc of width W = 6 zero crossings and rolloff 0.99:
+ *   y[m] = sum_{0 <= k < n} h(k / orig - m / new) x[k],   base = 0.99 min(orig, new),
+ *   h(t) = (base / orig) sinc(base t) cos^2(pi base t / (2 W)) for |base t| < W, else 0.
+ * With g = gcd(orig, new), orig_g = orig / g, new_g = new / g: output m = q new_g + p sums, in ascending k, the K inputs
+ * k = q orig_g + phase_start[p] + i against taps[p][i] (both built by the caller, device buffers: taps fp32 [new_g][K],
+ * phase_start int32 [new_g], non-decreasing in p with phase_start[new_g-1] <= phase_start[0] + orig_g).
+ * Utterance b holds n_samples[b] samples (device int32, 1 ..= N; NULL = N each): y[b, m] for m < ft_resample_out_len(
+ * n_samples[b], orig, new) exactly as the utterance resampled alone, zeros behind up to N_out; samples behind n_samples[b]
+ * are never read.  One launch, no atomics.  FT_EUNSUPPORTED when the table exceeds FT_RESAMPLE_MAX_PHASES phases or
+ * FT_RESAMPLE_MAX_TAPS taps in all (every ordered pair of 8 / 11.025 / 16 / 22.05 / 24 / 32 / 44.1 / 48 kHz fits). */
+#define FT_RESAMPLE_MAX_PHASES 2048
+#define FT_RESAMPLE_MAX_TAPS 20480
+int ft_resample_ragged(const float* x, const int32_t* n_samples, const float* taps, const int32_t* phase_start, float* y,
+                       int B, int N, int N_out, int orig_g, int new_g, int K, void* stream);
+/* host arithmetic only: ceil(n new / orig) in 64 bits; -1 for n < 0 or a rate < 1 */
+int64_t ft_resample_out_len(int64_t n, int orig, int new_rate);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

@@ -1,10 +1,15 @@
 """Host-side mirror of the reference audio front end (audio_processing.py:96-134, 172-235):
-TacotronSTFT.mel_spectrogram as ONE HIP kernel (ft_stft_mel: reflect pad + windowed radix-2 FFT
-in LDS + |X| + mel filterbank + log-compression) instead of a 1026x1024 dense-DFT conv1d.
+TacotronSTFT.mel_spectrogram as ONE HIP kernel (reflect pad + windowed real FFT in LDS + |X| + sparse mel
+filterbank + log-compression) instead of a 1026x1024 dense-DFT conv1d.  Two kernel families share the work
+(STFT._call picks one): ft_stft_r8 / ft_istft_r8 (csrc/stft_r8.hip) at n_fft 1024 with hop <= 256, and
+ft_stft_pow2 / ft_istft_pow2 (csrc/stft_pow2.hip) at every other setting with n_fft in POW2_NFFT and
+1 <= hop <= win_length <= n_fft; both sit on csrc/stft_common.h.  Only a mel spectrogram outside both (another
+n_fft, more than 128 mel channels, a signal no longer than n_fft / 2) falls to ft_stft_mel (csrc/stft.hip:
+complex radix-2 FFT + dense filterbank).
 
 The synthesis side (audio_processing.py:7-75, 237-270) is here too: STFT.inverse / STFT.forward run
-the inverse real FFT + overlap-add kernel ft_istft_r8, `griffin_lim` loops it with ft_stft_r8 on the
-device, and `window_sumsquare` is the reference's host function.  TacotronSTFT.mel_to_magnitude /
+the inverse real FFT + overlap-add kernel of the setting's family, `griffin_lim` loops it with the forward
+kernel on the device, and `window_sumsquare` is the reference's host function.  TacotronSTFT.mel_to_magnitude /
 mel_to_audio (not in the reference) turn model output into a waveform; the `_ragged` forms (STFT.transform_ragged /
 inverse_ragged, `griffin_lim_ragged`, mel_to_magnitude_ragged / mel_to_audio_ragged) do the same for a batch of utterances of
 different lengths in one launch per step.
@@ -338,10 +343,10 @@ POW2_NFFT = (256, 512, 1024, 2048, 4096)      # the analysis sizes of csrc/stft_
 
 class STFT(torch.nn.Module):
     """The reference STFT (audio_processing.py:172-270): `transform(y)` -> (magnitude, phase), both [B, n_fft/2+1, N // hop + 1]
-    (real FFT, ft_stft_r8), `inverse(magnitude, phase)` -> [B, 1, hop * (T - 1)] (inverse real FFT + overlap-add, ft_istft_r8)
-    and `forward(y)` = inverse(transform(y)); one HIP kernel each (csrc/stft_r8.hip).  fast_path(): n_fft 1024, hop <= 256;
-    pow2_path(): every other n_fft in POW2_NFFT with 1 <= hop <= win_length <= n_fft (ft_stft_pow2 / ft_istft_pow2,
-    csrc/stft_pow2.hip); any other setting raises NotImplementedError."""
+    (real FFT), `inverse(magnitude, phase)` -> [B, 1, hop * (T - 1)] (inverse real FFT + overlap-add) and `forward(y)` =
+    inverse(transform(y)); one HIP kernel each.  fast_path(): n_fft 1024, hop <= 256 (ft_stft_r8 / ft_istft_r8,
+    csrc/stft_r8.hip); pow2_path(): every other n_fft in POW2_NFFT with 1 <= hop <= win_length <= n_fft (ft_stft_pow2 /
+    ft_istft_pow2, csrc/stft_pow2.hip); any other setting raises NotImplementedError."""
 
     def __init__(self, filter_length=800, hop_length=200, win_length=800, window="hann"):
         super().__init__()
@@ -365,6 +370,16 @@ class STFT(torch.nn.Module):
                 "filter_length 1024 with any hop_length <= 256); got filter_length %d, hop_length %d, win_length %d"
                 % (what, "/".join(map(str, POW2_NFFT)), self.filter_length, self.hop_length, self.win_length))
 
+    def _call(self, base, tail, head, rest=()):
+        """The one place that knows the two kernel families: calls ft_<base>_r8<tail>(*head, hop, *rest, stream) on
+        fast_path() and ft_<base>_pow2<tail>(*head, n_fft, hop, win_length, *rest, stream) otherwise, looked up on the
+        library by name at call time."""
+        if self.fast_path():
+            name, geometry = "ft_%s_r8%s" % (base, tail), (self.hop_length,)
+        else:
+            name, geometry = "ft_%s_pow2%s" % (base, tail), (self.filter_length, self.hop_length, self.win_length)
+        L.check(getattr(L.lib(), name)(*head, *geometry, *rest, L.stream()), name)
+
     def transform(self, input_data):
         """audio_processing.py:207-235."""
         L.require_cuda(input_data)
@@ -376,12 +391,7 @@ class STFT(torch.nn.Module):
         n_frames = N // self.hop_length + 1
         mag = torch.empty(B, self.filter_length // 2 + 1, n_frames, device=y.device, dtype=torch.float32)
         phase = torch.empty_like(mag)
-        if self.fast_path():
-            L.check(L.lib().ft_stft_r8(L.ptr(y), L.ptr(self.fft_window), None, None, None, None, L.ptr(mag), L.ptr(phase), B,
-                                       N, self.hop_length, 0, L.stream()), "ft_stft_r8")
-        else:
-            L.check(L.lib().ft_stft_pow2(L.ptr(y), L.ptr(self.fft_window), None, None, None, None, L.ptr(mag), L.ptr(phase), B,
-                                         N, self.filter_length, self.hop_length, self.win_length, 0, L.stream()), "ft_stft_pow2")
+        self._call("stft", "", (L.ptr(y), L.ptr(self.fft_window), None, None, None, None, L.ptr(mag), L.ptr(phase), B, N), (0,))
         return mag, phase
 
     def _check_spectrum(self, magnitude, phase):
@@ -400,12 +410,8 @@ class STFT(torch.nn.Module):
             self.to(m.device)
         B, _, T = m.shape
         y = torch.empty(B, 1, self.hop_length * max(T - 1, 0), device=m.device, dtype=torch.float32)
-        if T >= 2 and self.fast_path():                 # one frame leaves nothing after the two n_fft/2-sample trims
-            L.check(L.lib().ft_istft_r8(L.ptr(m), L.ptr(ph), L.ptr(self.fft_window), L.ptr(y), B, T, self.hop_length,
-                                        L.stream()), "ft_istft_r8")
-        elif T >= 2:
-            L.check(L.lib().ft_istft_pow2(L.ptr(m), L.ptr(ph), L.ptr(self.fft_window), L.ptr(y), B, T, self.filter_length,
-                                          self.hop_length, self.win_length, L.stream()), "ft_istft_pow2")
+        if T >= 2:                                      # one frame leaves nothing after the two n_fft/2-sample trims
+            self._call("istft", "", (L.ptr(m), L.ptr(ph), L.ptr(self.fft_window), L.ptr(y), B, T))
         return y
 
     def _transform_ragged(self, y, ns, want_magnitude=True):
@@ -413,13 +419,7 @@ class STFT(torch.nn.Module):
         B, N = y.shape
         phase = torch.empty(B, self.filter_length // 2 + 1, N // self.hop_length + 1, device=y.device, dtype=torch.float32)
         mag = torch.empty_like(phase) if want_magnitude else None
-        if self.fast_path():
-            L.check(L.lib().ft_stft_r8_ragged_phase(L.ptr(y), L.ptr(ns), L.ptr(self.fft_window), L.ptr(mag), L.ptr(phase), B, N,
-                                                    self.hop_length, L.stream()), "ft_stft_r8_ragged_phase")
-        else:
-            L.check(L.lib().ft_stft_pow2_ragged_phase(L.ptr(y), L.ptr(ns), L.ptr(self.fft_window), L.ptr(mag), L.ptr(phase), B, N,
-                                                      self.filter_length, self.hop_length, self.win_length, L.stream()),
-                    "ft_stft_pow2_ragged_phase")
+        self._call("stft", "_ragged_phase", (L.ptr(y), L.ptr(ns), L.ptr(self.fft_window), L.ptr(mag), L.ptr(phase), B, N))
         return mag, phase
 
     def transform_ragged(self, input_data, n_samples):
@@ -443,13 +443,8 @@ class STFT(torch.nn.Module):
         """m, ph [B, n_fft/2+1, T] contiguous fp32, nf [B] int32 on the device -> [B, hop * (T - 1)]: one launch."""
         B, _, T = m.shape
         y = torch.empty(B, self.hop_length * max(T - 1, 0), device=m.device, dtype=torch.float32)
-        if T >= 2 and self.fast_path():                 # one frame leaves nothing after the two n_fft/2-sample trims
-            L.check(L.lib().ft_istft_r8_ragged(L.ptr(m), L.ptr(ph), L.ptr(nf), L.ptr(self.fft_window), L.ptr(y), B, T,
-                                               self.hop_length, L.stream()), "ft_istft_r8_ragged")
-        elif T >= 2:
-            L.check(L.lib().ft_istft_pow2_ragged(L.ptr(m), L.ptr(ph), L.ptr(nf), L.ptr(self.fft_window), L.ptr(y), B, T,
-                                                 self.filter_length, self.hop_length, self.win_length, L.stream()),
-                    "ft_istft_pow2_ragged")
+        if T >= 2:                                      # one frame leaves nothing after the two n_fft/2-sample trims
+            self._call("istft", "_ragged", (L.ptr(m), L.ptr(ph), L.ptr(nf), L.ptr(self.fft_window), L.ptr(y), B, T))
         return y
 
     def inverse_ragged(self, magnitude, phase, n_frames):
@@ -511,14 +506,8 @@ class TacotronSTFT(torch.nn.Module):
                                       "or n_fft in %s with 1 <= hop <= win_length <= n_fft" % (POW2_NFFT,))
         mel = torch.empty(B, self.n_mel_channels, T_out, device=y.device, dtype=torch.float32)
         ns = n_samples.to(torch.int32)
-        if st.fast_path():
-            L.check(L.lib().ft_stft_r8_ragged(L.ptr(y), L.ptr(ns), L.ptr(st.fft_window), L.ptr(self.fb_bin0), L.ptr(self.fb_ptr),
-                                              L.ptr(self.fb_w), L.ptr(mel), B, N, st.hop_length, self.n_mel_channels, T_out,
-                                              L.stream()), "ft_stft_r8_ragged")
-        else:
-            L.check(L.lib().ft_stft_pow2_ragged(L.ptr(y), L.ptr(ns), L.ptr(st.fft_window), L.ptr(self.fb_bin0), L.ptr(self.fb_ptr),
-                                                L.ptr(self.fb_w), L.ptr(mel), B, N, st.filter_length, st.hop_length, st.win_length,
-                                                self.n_mel_channels, T_out, L.stream()), "ft_stft_pow2_ragged")
+        st._call("stft", "_ragged", (L.ptr(y), L.ptr(ns), L.ptr(st.fft_window), L.ptr(self.fb_bin0), L.ptr(self.fb_ptr),
+                                     L.ptr(self.fb_w), L.ptr(mel), B, N), (self.n_mel_channels, T_out))
         return mel
 
     def ragged_path(self):
@@ -541,16 +530,12 @@ class TacotronSTFT(torch.nn.Module):
         st = self.stft_fn
         n_frames = N // st.hop_length + 1
         mel = torch.empty(B, self.n_mel_channels, n_frames, device=y.device, dtype=torch.float32)
-        if st.fast_path() and self.n_mel_channels <= 128 and N > st.filter_length // 2:
-            # rFFT (512-point complex FFT + split) + sparse triangular filterbank, one wave per frame (csrc/stft_r8.hip)
-            L.check(L.lib().ft_stft_r8(L.ptr(y), L.ptr(st.fft_window), L.ptr(self.fb_bin0), L.ptr(self.fb_ptr), L.ptr(self.fb_w),
-                                       L.ptr(mel), None, None, B, N, st.hop_length, self.n_mel_channels, L.stream()), "ft_stft_r8")
-        elif st.pow2_path() and self.n_mel_channels <= 128 and N > st.filter_length // 2:
-            # the same rFFT design for any power-of-two n_fft and hop (csrc/stft_pow2.hip); mel_spectrogram_ragged shares it
-            L.check(L.lib().ft_stft_pow2(L.ptr(y), L.ptr(st.fft_window), L.ptr(self.fb_bin0), L.ptr(self.fb_ptr), L.ptr(self.fb_w),
-                                         L.ptr(mel), None, None, B, N, st.filter_length, st.hop_length, st.win_length,
-                                         self.n_mel_channels, L.stream()), "ft_stft_pow2")
-        else:                                           # general n_fft: complex radix-2 FFT + dense filterbank (csrc/stft.hip)
+        if self.ragged_path() and N > st.filter_length // 2:
+            # rFFT (n_fft/2-point complex FFT + split) + sparse triangular filterbank, one wave per frame (csrc/stft_r8.hip at
+            # 1024 with hop <= 256, csrc/stft_pow2.hip at the other power-of-two settings); mel_spectrogram_ragged shares it
+            st._call("stft", "", (L.ptr(y), L.ptr(st.fft_window), L.ptr(self.fb_bin0), L.ptr(self.fb_ptr), L.ptr(self.fb_w),
+                                  L.ptr(mel), None, None, B, N), (self.n_mel_channels,))
+        else:                                           # outside both: complex radix-2 FFT + dense filterbank (csrc/stft.hip)
             L.check(L.lib().ft_stft_mel(L.ptr(y), L.ptr(st.fft_window), L.ptr(self.mel_basis), L.ptr(mel), B, N,
                                         st.filter_length, st.hop_length, self.n_mel_channels, L.stream()), "ft_stft_mel")
         return mel

@@ -22,42 +22,10 @@
 namespace {
 
 constexpr int WAVES = 4;
-constexpr int BWMAX = 2048;                            // CSR values staged in LDS when they fit
 constexpr int LDS_TWO_PER_CU = 80 * 1024;              // forward: prefer an LDS footprint that leaves room for two workgroups
 constexpr int LDS_MAX = 160 * 1024;
 
-struct cpx { float re, im; };
-__device__ __forceinline__ cpx cmul(cpx a, cpx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-__device__ __forceinline__ cpx cadd(cpx a, cpx b) { return {a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ cpx csub(cpx a, cpx b) { return {a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ cpx mul_mi(cpx a) { return {a.im, -a.re}; }                       // a * (-i)
-
-__device__ __forceinline__ void lds_order() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// in-place forward DFT of R = 2, 4, 8 points (e^{-2 pi i jk/R}), natural order in and out
-__device__ __forceinline__ void dft(cpx (&v)[2]) {
-    const cpx a = v[0];
-    v[0] = cadd(a, v[1]);
-    v[1] = csub(a, v[1]);
-}
-__device__ __forceinline__ void dft(cpx (&v)[4]) {
-    const cpx a0 = cadd(v[0], v[2]), a1 = csub(v[0], v[2]), a2 = cadd(v[1], v[3]), a3 = mul_mi(csub(v[1], v[3]));
-    v[0] = cadd(a0, a2); v[2] = csub(a0, a2);
-    v[1] = cadd(a1, a3); v[3] = csub(a1, a3);
-}
-__device__ __forceinline__ void dft(cpx (&v)[8]) {
-    const float r = 0.70710678118654752f;
-    cpx a0 = cadd(v[0], v[4]), a1 = csub(v[0], v[4]), a2 = cadd(v[2], v[6]), a3 = mul_mi(csub(v[2], v[6]));
-    cpx a4 = cadd(v[1], v[5]), a5 = csub(v[1], v[5]), a6 = cadd(v[3], v[7]), a7 = mul_mi(csub(v[3], v[7]));
-    cpx b0 = cadd(a0, a2), b2 = csub(a0, a2), b1 = cadd(a1, a3), b3 = csub(a1, a3);
-    cpx b4 = cadd(a4, a6), b6 = mul_mi(csub(a4, a6)), b5 = cadd(a5, a7), b7 = csub(a5, a7);
-    b5 = (cpx){r * (b5.re + b5.im), r * (b5.im - b5.re)};                                     // * e^{-i pi/4}
-    b7 = (cpx){r * (b7.im - b7.re), -r * (b7.re + b7.im)};                                    // * e^{-3 i pi/4}
-    v[0] = cadd(b0, b4); v[4] = csub(b0, b4);
-    v[1] = cadd(b1, b5); v[5] = csub(b1, b5);
-    v[2] = cadd(b2, b6); v[6] = csub(b2, b6);
-    v[3] = cadd(b3, b7); v[7] = csub(b3, b7);
-}
+#include "stft_common.h"
 
 // tw[j] = e^{-2 pi i j / N}, j = 0 .. H (N = 2H): the split twiddles, and W_H^j = tw[2j] for the FFT passes
 template <int H>
@@ -120,16 +88,6 @@ __device__ __forceinline__ void fft_wave(cpx* T, const cpx* tw, int lane) {
     fft_pass<H, R0, 1>(T, tw, lane);
     fft_r8_passes<H, R0>(T, tw, lane);
 }
-
-struct StftP {
-    const float* y; const float* window;
-    const int* band_bin0; const int* band_ptr; const float* band_w;      // CSR of the filterbank: band b covers bins
-    float* mel; float* mag; float* phase;                                // [bin0[b], bin0[b] + ptr[b+1] - ptr[b])
-    int N, hop, n_mel, n_frames;
-    const int* n_samples;            // ragged batch: utterance b holds n_samples[b] <= N samples and n_samples[b] / hop + 1
-    int ldt;                         // frames; frames beyond that are written as zeros; ldt = output row stride
-    int fpw;                         // frames per wave
-};                                   // phase without mag (ft_stft_pow2_ragged_phase): the magnitude store is skipped
 
 // dynamic LDS of the forward kernel: tw [H+1] cpx | T [WAVES][H] cpx | mo [n_mel][FPG+1] | bw [BWMAX] | xs [span]
 size_t stft_lds_bytes(int n_fft, int hop, int n_mel, bool mel, int fpw) {
@@ -274,13 +232,6 @@ __global__ __launch_bounds__(256) void stft_pow2_k(StftP p) {
 //     result does not depend on the launch.
 constexpr int SPT = 16, OWN = 256 * SPT;
 
-struct IstftP {
-    const float* mag; const float* phase; const float* window;
-    float* y;
-    int T, hop, n_out;               // T: frames per spectrum row (the row stride), n_out = hop (T - 1): samples per output row
-    const int* n_frames;             // ragged batch (ft_istft_pow2_ragged): utterance b holds n_frames[b] <= T frames; later frames are
-};                                   // never read and the samples from hop (n_frames[b] - 1) on are written as zeros
-
 // dynamic LDS of the inverse kernel: tw [H+1] cpx | X [WAVES][H+1] cpx | wl [N]
 size_t istft_lds_bytes(int n_fft) {
     const size_t H = n_fft / 2;
@@ -327,13 +278,7 @@ __global__ __launch_bounds__(256) void istft_pow2_k(IstftP p) {
                 if (k <= H) X[k] = (cpx){magb[(size_t)k * ldt + t], phb[(size_t)k * ldt + t]};
             }
             lds_order();
-#pragma unroll 1
-            for (int k = lane; k <= H; k += 64) {
-                const cpx mp = X[k];
-                float s, c;
-                sincosf(mp.im, &s, &c);
-                X[k] = (cpx){mp.re * c, (k & (H - 1)) == 0 ? 0.f : mp.re * s};
-            }
+            polar_to_cpx(X, H, lane);
             lds_order();
             // ---- inverse split: conj Z[k], k = lane + 64 j < H; all reads before the in-place writes
             cpx v[PL];
@@ -388,11 +333,6 @@ __global__ __launch_bounds__(256) void istft_pow2_k(IstftP p) {
     }
 }
 
-int log2_pow2_nfft(int n_fft) {                       // 8 .. 12 for n_fft = 256 .. 4096, -1 otherwise
-    for (int l = 8; l <= 12; ++l) if (n_fft == (1 << l)) return l;
-    return -1;
-}
-
 template <int LH>
 int launch_stft(const StftP& p, int B, hipStream_t s) {
     const int fpg = WAVES * p.fpw;
@@ -400,17 +340,15 @@ int launch_stft(const StftP& p, int B, hipStream_t s) {
     FT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(stft_pow2_k<LH>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      LDS_MAX));
     hipLaunchKernelGGL(stft_pow2_k<LH>, dim3(cdiv(p.n_frames, fpg), B), dim3(256), lds, s, p);
-    FT_CHECK_LAUNCH();
     return FT_OK;
 }
 
-int stft_dispatch(StftP p, int B, int n_fft, void* stream) {
+int stft_dispatch(StftP p, int B, int n_fft, hipStream_t s) {
     int fpw = 4;
     while (fpw > 1 && stft_lds_bytes(n_fft, p.hop, p.n_mel, p.mel != nullptr, fpw) > LDS_TWO_PER_CU) fpw /= 2;
     const size_t lds = stft_lds_bytes(n_fft, p.hop, p.n_mel, p.mel != nullptr, fpw);
     if (lds > LDS_MAX) return ft_fail(FT_EUNSUPPORTED, "stft_pow2: n_fft=%d hop=%d needs %zu B of LDS", n_fft, p.hop, lds);
     p.fpw = fpw;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (log2_pow2_nfft(n_fft)) {
         case 8: return launch_stft<7>(p, B, s);
         case 9: return launch_stft<8>(p, B, s);
@@ -426,12 +364,10 @@ int launch_istft(const IstftP& p, int B, hipStream_t s) {
     FT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(istft_pow2_k<LH>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      LDS_MAX));
     hipLaunchKernelGGL(istft_pow2_k<LH>, dim3(cdiv(p.n_out, OWN), B), dim3(256), lds, s, p);
-    FT_CHECK_LAUNCH();
     return FT_OK;
 }
 
-int istft_dispatch(const IstftP& p, int B, int n_fft, void* stream) {
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+int istft_dispatch(const IstftP& p, int B, int n_fft, hipStream_t s) {
     switch (log2_pow2_nfft(n_fft)) {
         case 8: return launch_istft<7>(p, B, s);
         case 9: return launch_istft<8>(p, B, s);
@@ -441,6 +377,9 @@ int istft_dispatch(const IstftP& p, int B, int n_fft, void* stream) {
     }
 }
 
+// the entries below are the shared launch path (stft_common.h); hop <= win_length <= n_fft is the only limit on the hop
+const StftFamily POW2 = {stft_dispatch, istft_dispatch, 4096, OWN};
+
 }  // namespace
 
 // y [B,N] -> any of mel [B,n_mel,T] (needs the CSR filterbank), mag [B,n_fft/2+1,T], phase [B,n_fft/2+1,T] (both or neither);
@@ -449,14 +388,8 @@ int istft_dispatch(const IstftP& p, int B, int n_fft, void* stream) {
 extern "C" int ft_stft_pow2(const float* y, const float* window, const int32_t* band_bin0, const int32_t* band_ptr,
                             const float* band_w, float* mel, float* mag, float* phase, int B, int N, int n_fft, int hop,
                             int win_length, int n_mel, void* stream) {
-    FT_CHECK_ARG(y && window && (mel || mag));
-    FT_CHECK_ARG((mag == nullptr) == (phase == nullptr));
-    FT_CHECK_ARG(!mel || (band_bin0 && band_ptr && band_w && n_mel >= 1 && n_mel <= 128));
-    FT_CHECK_ARG(log2_pow2_nfft(n_fft) > 0 && hop >= 1 && hop <= win_length && win_length <= n_fft);
-    FT_CHECK_ARG(B >= 1 && B <= 65535 && N > n_fft / 2);
-    const int n_frames = N / hop + 1;
-    StftP p{y, window, band_bin0, band_ptr, band_w, mel, mag, phase, N, hop, mel ? n_mel : 0, n_frames, nullptr, n_frames, 1};
-    return stft_dispatch(p, B, n_fft, stream);
+    return stft_forward(__func__, POW2, y, nullptr, false, window, band_bin0, band_ptr, band_w, mel, mag, phase, B, N, n_fft, hop,
+                        win_length, n_mel, nullptr, stream);
 }
 
 // The collated batch of the data path, as ft_stft_r8_ragged: y [B,N] zero-padded audio, utterance b holds n_samples[b] samples
@@ -465,11 +398,8 @@ extern "C" int ft_stft_pow2(const float* y, const float* window, const int32_t* 
 extern "C" int ft_stft_pow2_ragged(const float* y, const int32_t* n_samples, const float* window, const int32_t* band_bin0,
                                    const int32_t* band_ptr, const float* band_w, float* mel, int B, int N, int n_fft, int hop,
                                    int win_length, int n_mel, int T_out, void* stream) {
-    FT_CHECK_ARG(y && n_samples && window && mel && band_bin0 && band_ptr && band_w && n_mel >= 1 && n_mel <= 128);
-    FT_CHECK_ARG(log2_pow2_nfft(n_fft) > 0 && hop >= 1 && hop <= win_length && win_length <= n_fft);
-    FT_CHECK_ARG(B >= 1 && B <= 65535 && N > n_fft / 2 && T_out >= 1);
-    StftP p{y, window, band_bin0, band_ptr, band_w, mel, nullptr, nullptr, N, hop, n_mel, T_out, n_samples, T_out, 1};
-    return stft_dispatch(p, B, n_fft, stream);
+    return stft_forward(__func__, POW2, y, n_samples, true, window, band_bin0, band_ptr, band_w, mel, nullptr, nullptr, B, N, n_fft,
+                        hop, win_length, n_mel, &T_out, stream);
 }
 
 // The spectrum of a ragged batch, as ft_stft_r8_ragged_phase: y [B,N], utterance b holds n_samples[b] samples (device int32) ->
@@ -478,24 +408,15 @@ extern "C" int ft_stft_pow2_ragged(const float* y, const int32_t* n_samples, con
 // that is written.  Same preconditions as ft_stft_pow2.
 extern "C" int ft_stft_pow2_ragged_phase(const float* y, const int32_t* n_samples, const float* window, float* mag, float* phase,
                                          int B, int N, int n_fft, int hop, int win_length, void* stream) {
-    FT_CHECK_ARG(y && n_samples && window && phase);
-    FT_CHECK_ARG(log2_pow2_nfft(n_fft) > 0 && hop >= 1 && hop <= win_length && win_length <= n_fft);
-    FT_CHECK_ARG(B >= 1 && B <= 65535 && N > n_fft / 2);
-    const int n_frames = N / hop + 1;
-    StftP p{y, window, nullptr, nullptr, nullptr, nullptr, mag, phase, N, hop, 0, n_frames, n_samples, n_frames, 1};
-    return stft_dispatch(p, B, n_fft, stream);
+    return stft_forward(__func__, POW2, y, n_samples, true, window, nullptr, nullptr, nullptr, nullptr, mag, phase, B, N, n_fft, hop,
+                        win_length, 0, nullptr, stream);
 }
 
 // (mag, phase) [B,n_fft/2+1,T] -> y [B, hop (T-1)]: STFT.inverse (audio_processing.py:237-263) for n_fft = 256 .. 4096 (a power
 // of two), 1 <= hop <= win_length <= n_fft; window: hann [n_fft] (win_length zero-padded by the caller), as ft_stft_pow2.
 extern "C" int ft_istft_pow2(const float* mag, const float* phase, const float* window, float* y, int B, int T, int n_fft,
                              int hop, int win_length, void* stream) {
-    FT_CHECK_ARG(mag && phase && window && y);
-    FT_CHECK_ARG(log2_pow2_nfft(n_fft) > 0 && hop >= 1 && hop <= win_length && win_length <= n_fft);
-    FT_CHECK_ARG(B >= 1 && B <= 65535 && T >= 2);
-    FT_CHECK_ARG((int64_t)hop * (T - 1) <= INT32_MAX - 2 * n_fft - OWN);
-    const int n_out = hop * (T - 1);
-    return istft_dispatch(IstftP{mag, phase, window, y, T, hop, n_out, nullptr}, B, n_fft, stream);
+    return stft_inverse(__func__, POW2, mag, phase, nullptr, false, window, y, B, T, n_fft, hop, win_length, stream);
 }
 
 // The inverse of a ragged batch, as ft_istft_r8_ragged: (mag, phase) [B,n_fft/2+1,T] with row stride T, utterance b holds
@@ -504,10 +425,5 @@ extern "C" int ft_istft_pow2(const float* mag, const float* phase, const float* 
 // launch for the batch, no atomics, launch-independent.  Same preconditions as ft_istft_pow2.
 extern "C" int ft_istft_pow2_ragged(const float* mag, const float* phase, const int32_t* n_frames, const float* window, float* y,
                                     int B, int T, int n_fft, int hop, int win_length, void* stream) {
-    FT_CHECK_ARG(mag && phase && n_frames && window && y);
-    FT_CHECK_ARG(log2_pow2_nfft(n_fft) > 0 && hop >= 1 && hop <= win_length && win_length <= n_fft);
-    FT_CHECK_ARG(B >= 1 && B <= 65535 && T >= 2);
-    FT_CHECK_ARG((int64_t)hop * (T - 1) <= INT32_MAX - 2 * n_fft - OWN);
-    const int n_out = hop * (T - 1);
-    return istft_dispatch(IstftP{mag, phase, window, y, T, hop, n_out, n_frames}, B, n_fft, stream);
+    return stft_inverse(__func__, POW2, mag, phase, n_frames, true, window, y, B, T, n_fft, hop, win_length, stream);
 }

@@ -21,28 +21,8 @@ namespace {
 constexpr int NFFT = 1024, NH = 512, NB = 513;
 constexpr int FPW = 4, FPG = 4 * FPW;                  // frames per wave / per workgroup
 constexpr int SPAN = (FPG - 1) * 256 + NFFT;           // hop is a runtime argument <= 256 in the reference; sized for 256
-constexpr int BWMAX = 2048;                            // CSR values staged in LDS when they fit (Slaney, 80 bands: ~1 000)
 
-struct cpx { float re, im; };
-__device__ __forceinline__ cpx cmul(cpx a, cpx b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
-__device__ __forceinline__ cpx cadd(cpx a, cpx b) { return {a.re + b.re, a.im + b.im}; }
-__device__ __forceinline__ cpx csub(cpx a, cpx b) { return {a.re - b.re, a.im - b.im}; }
-__device__ __forceinline__ cpx mul_mi(cpx a) { return {a.im, -a.re}; }                       // a * (-i)
-
-// in-place forward DFT of 8 points (e^{-2 pi i jk/8}), natural order in and out
-__device__ __forceinline__ void dft8(cpx (&v)[8]) {
-    const float r = 0.70710678118654752f;
-    cpx a0 = cadd(v[0], v[4]), a1 = csub(v[0], v[4]), a2 = cadd(v[2], v[6]), a3 = mul_mi(csub(v[2], v[6]));
-    cpx a4 = cadd(v[1], v[5]), a5 = csub(v[1], v[5]), a6 = cadd(v[3], v[7]), a7 = mul_mi(csub(v[3], v[7]));
-    cpx b0 = cadd(a0, a2), b2 = csub(a0, a2), b1 = cadd(a1, a3), b3 = csub(a1, a3);
-    cpx b4 = cadd(a4, a6), b6 = mul_mi(csub(a4, a6)), b5 = cadd(a5, a7), b7 = csub(a5, a7);
-    b5 = (cpx){r * (b5.re + b5.im), r * (b5.im - b5.re)};                                     // * e^{-i pi/4}
-    b7 = (cpx){r * (b7.im - b7.re), -r * (b7.re + b7.im)};                                    // * e^{-3 i pi/4}
-    v[0] = cadd(b0, b4); v[4] = csub(b0, b4);
-    v[1] = cadd(b1, b5); v[5] = csub(b1, b5);
-    v[2] = cadd(b2, b6); v[6] = csub(b2, b6);
-    v[3] = cadd(b3, b7); v[7] = csub(b3, b7);
-}
+#include "stft_common.h"
 
 // The per-lane twiddle constants of fft512_r8 and the split step depend on (lane, k) only; a workgroup evaluates each once into
 // LDS (1 152 sincospif over 256 threads): tw[0, 512) = W512^{l k}, tw[512, 576) = W64^{b k}, tw[576, 1152) = W1024^{k}.
@@ -62,7 +42,7 @@ __device__ __forceinline__ void fill_twiddles(cpx* tw, int tid) {
 // through LDS, DFT_8 over a, twiddle w2 = W64^{b k2}, transpose, DFT_8 over b).  T: the wave's own 512-entry LDS buffer; the
 // LDS operations of one wave execute in order, so no barrier is needed.
 __device__ __forceinline__ void fft512_r8(cpx (&v)[8], cpx* T, const cpx (&w1)[8], const cpx (&w2)[8], int lane) {
-    dft8(v);
+    dft(v);
 #pragma unroll
     for (int k = 1; k < 8; ++k) v[k] = cmul(v[k], w1[k]);
     // transpose 1: element (l = 8 a + b2, k1) -> lane (k1, b2), register a
@@ -71,12 +51,12 @@ __device__ __forceinline__ void fft512_r8(cpx (&v)[8], cpx* T, const cpx (&w1)[8
 #pragma unroll
         for (int k1 = 0; k1 < 8; ++k1) T[(k1 * 8 + b2) * 8 + a] = v[k1];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lds_order();
 #pragma unroll
     for (int a = 0; a < 8; ++a) v[a] = T[lane * 8 + a];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lds_order();
     // pass 2: DFT over a; twiddle W64^{b2 k2}
-    dft8(v);
+    dft(v);
 #pragma unroll
     for (int k = 1; k < 8; ++k) v[k] = cmul(v[k], w2[k]);
     // transpose 2: element (k1, b2, k2) -> lane (k1, k2), register b2
@@ -85,22 +65,13 @@ __device__ __forceinline__ void fft512_r8(cpx (&v)[8], cpx* T, const cpx (&w1)[8
 #pragma unroll
         for (int k2 = 0; k2 < 8; ++k2) T[(k1 * 8 + k2) * 8 + b2] = v[k2];
     }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lds_order();
 #pragma unroll
     for (int b2 = 0; b2 < 8; ++b2) v[b2] = T[lane * 8 + b2];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    lds_order();
     // pass 3: DFT over b2
-    dft8(v);
+    dft(v);
 }
-
-struct StftP {
-    const float* y; const float* window;
-    const int* band_bin0; const int* band_ptr; const float* band_w;      // CSR of the filterbank: band b covers bins
-    float* mel; float* mag; float* phase;                                // [bin0[b], bin0[b] + ptr[b+1] - ptr[b])
-    int N, hop, n_mel, n_frames;
-    const int* n_samples;            // ragged batch (ft_stft_r8_ragged): utterance b holds n_samples[b] <= N samples and
-    int ldt;                         // n_samples[b] / hop + 1 frames; frames beyond that are written as zeros; ldt = output row stride
-};                                   // phase without mag (ft_stft_r8_ragged_phase): the magnitude store is skipped
 
 __global__ __launch_bounds__(256) void stft_r8_k(StftP p) {
     __shared__ __attribute__((aligned(16))) float xs[SPAN];
@@ -184,7 +155,7 @@ __global__ __launch_bounds__(256) void stft_r8_k(StftP p) {
 #pragma unroll
             for (int k3 = 0; k3 < 8; ++k3) T[q + 64 * k3] = v[k3];
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lds_order();
         // ---- split: X[k], k = lane + 64 r (r = 0 .. 7), and k = 512 on lane 0
 #pragma unroll
         for (int r = 0; r <= 8; ++r) {
@@ -203,7 +174,7 @@ __global__ __launch_bounds__(256) void stft_r8_k(StftP p) {
                 }
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lds_order();
         // ---- sparse triangular filterbank + log compression (audio_processing.py:132-133, :81-82)
         if (p.mel) {
 #pragma unroll
@@ -230,7 +201,7 @@ __global__ __launch_bounds__(256) void stft_r8_k(StftP p) {
                 mo[mb][wave * FPW + fi] = logf(fmaxf(s, 1e-5f));
             }
         }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lds_order();
     }
     if (p.phase && p.n_samples) {                                         // a ragged spectrum is zero behind the utterance's last frame
         const int te = min(f0 + (wave + 1) * FPW, p.n_frames);
@@ -251,52 +222,6 @@ __global__ __launch_bounds__(256) void stft_r8_k(StftP p) {
 }
 
 }  // namespace
-
-// y [B,N] -> any of mel [B,n_mel,T] (needs the CSR filterbank), mag [B,513,T], phase [B,513,T] (both or neither); T = N / hop + 1.
-// n_fft = 1024 (hann window [1024] passed in, any win_length zero-padded by the caller), hop <= 256.
-extern "C" int ft_stft_r8(const float* y, const float* window, const int32_t* band_bin0, const int32_t* band_ptr,
-                          const float* band_w, float* mel, float* mag, float* phase, int B, int N, int hop, int n_mel,
-                          void* stream) {
-    FT_CHECK_ARG(y && window && (mel || mag));
-    FT_CHECK_ARG((mag == nullptr) == (phase == nullptr));
-    FT_CHECK_ARG(!mel || (band_bin0 && band_ptr && band_w && n_mel >= 1 && n_mel <= 128));
-    FT_CHECK_ARG(B >= 1 && B <= 65535 && hop >= 1 && hop <= 256 && N > NH);
-    const int n_frames = N / hop + 1;
-    StftP p{y, window, band_bin0, band_ptr, band_w, mel, mag, phase, N, hop, n_mel, n_frames, nullptr, n_frames};
-    hipLaunchKernelGGL(stft_r8_k, dim3(cdiv(n_frames, FPG), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
-    FT_CHECK_LAUNCH();
-    return FT_OK;
-}
-
-// The collated batch of the data path (data.py:207-229 pads every mel with zeros to the longest one): y [B,N] zero-padded audio,
-// utterance b holds n_samples[b] samples (device int32) -> mel [B,n_mel,T_out]: frames < n_samples[b] / hop + 1 as ft_stft_r8
-// computes them for that utterance alone (reflection about ITS last sample), zeros beyond.  ONE launch for the batch instead of
-// one per utterance (each ~35 us of latency for <= 862 frames).  T_out >= max_b (n_samples[b] / hop + 1).
-extern "C" int ft_stft_r8_ragged(const float* y, const int32_t* n_samples, const float* window, const int32_t* band_bin0,
-                                 const int32_t* band_ptr, const float* band_w, float* mel, int B, int N, int hop, int n_mel,
-                                 int T_out, void* stream) {
-    FT_CHECK_ARG(y && n_samples && window && mel && band_bin0 && band_ptr && band_w && n_mel >= 1 && n_mel <= 128);
-    FT_CHECK_ARG(B >= 1 && B <= 65535 && hop >= 1 && hop <= 256 && N > NH && T_out >= 1);
-    StftP p{y, window, band_bin0, band_ptr, band_w, mel, nullptr, nullptr, N, hop, n_mel, T_out, n_samples, T_out};
-    hipLaunchKernelGGL(stft_r8_k, dim3(cdiv(T_out, FPG), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
-    FT_CHECK_LAUNCH();
-    return FT_OK;
-}
-
-// The spectrum of a ragged batch (the analysis step of griffin_lim_ragged): y [B,N], utterance b holds n_samples[b] samples
-// (device int32) -> mag (NULL = skip the store: Griffin-Lim keeps the phase only) and phase [B,513,T_out], T_out = N / hop + 1:
-// frames < n_samples[b] / hop + 1 exactly as ft_stft_r8 computes them for y[b, :n_samples[b]] alone (reflection about ITS last
-// sample, so the samples behind it are never read), zeros beyond in every output that is written.  ONE launch for the batch.
-extern "C" int ft_stft_r8_ragged_phase(const float* y, const int32_t* n_samples, const float* window, float* mag, float* phase,
-                                       int B, int N, int hop, void* stream) {
-    FT_CHECK_ARG(y && n_samples && window && phase);
-    FT_CHECK_ARG(B >= 1 && B <= 65535 && hop >= 1 && hop <= 256 && N > NH);
-    const int n_frames = N / hop + 1;
-    StftP p{y, window, nullptr, nullptr, nullptr, nullptr, mag, phase, N, hop, 0, n_frames, n_samples, n_frames};
-    hipLaunchKernelGGL(stft_r8_k, dim3(cdiv(n_frames, FPG), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
-    FT_CHECK_LAUNCH();
-    return FT_OK;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Inverse STFT (audio_processing.py:237-263, STFT.inverse) for the same setting: (magnitude, phase) [B,513,T] -> y [B,hop*(T-1)],
@@ -319,13 +244,6 @@ namespace {
 
 constexpr int FC = 8;                                  // frames staged in LDS per round: 2 per wave
 constexpr int SPT = 16;                                // owned samples per thread: 16 hop <= 4 096 = 256 threads x 16
-
-struct IstftP {
-    const float* mag; const float* phase; const float* window;
-    float* y;
-    int T, hop, n_out;               // T: frames per spectrum row (the row stride), n_out = hop (T - 1): samples per output row
-    const int* n_frames;             // ragged batch (ft_istft_r8_ragged): utterance b holds n_frames[b] <= T frames; later frames are
-};                                   // never read and the samples from hop (n_frames[b] - 1) on are written as zeros
 
 __global__ __launch_bounds__(256) void istft_r8_k(IstftP p) {
     __shared__ __attribute__((aligned(16))) float fr[FC][NFFT];          // windowed irfft of the round's frames
@@ -383,15 +301,9 @@ __global__ __launch_bounds__(256) void istft_r8_k(IstftP p) {
                 X[lane + 64 * j] = (cpx){magb[o], phb[o]};
             }
             if (lane == 0) X[NH] = (cpx){magb[(size_t)NH * ldt + t], phb[(size_t)NH * ldt + t]};
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll 1
-            for (int k = lane; k <= NH; k += 64) {
-                const cpx mp = X[k];
-                float s, c;
-                sincosf(mp.im, &s, &c);
-                X[k] = (cpx){mp.re * c, (k & (NH - 1)) == 0 ? 0.f : mp.re * s};
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_order();
+            polar_to_cpx(X, NH, lane);
+            lds_order();
             // ---- inverse split: conj Z[k] for k = lane + 64 j (the input layout of fft512_r8)
             cpx v[8];
 #pragma unroll
@@ -403,7 +315,7 @@ __global__ __launch_bounds__(256) void istft_r8_k(IstftP p) {
                 const cpx e = cmul((cpx){w3[j].re, -w3[j].im}, d);                      // e^{+2 pi i k / 1024} d
                 v[j] = (cpx){s.re - e.im, -(s.im + e.re)};                               // conj(s + i e)
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_order();
             fft512_r8(v, X, w1, w2, lane);
             // ---- v[k3] = conj(2 * 512 z[m]), m = q + 64 k3: x[2m] = Re, x[2m+1] = -Im, scaled by 1/1024 (exact) and windowed
             float* F = fr[f];
@@ -413,7 +325,7 @@ __global__ __launch_bounds__(256) void istft_r8_k(IstftP p) {
                 *reinterpret_cast<float2*>(F + 2 * m) =
                     make_float2(win[k3].x * (v[k3].re * (1.0f / 1024.0f)), win[k3].y * (-v[k3].im * (1.0f / 1024.0f)));
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_order();
         }
         __syncthreads();
         // ---- overlap-add of this round's frames, ascending t
@@ -446,20 +358,56 @@ __global__ __launch_bounds__(256) void istft_r8_k(IstftP p) {
     }
 }
 
+int launch_stft_r8(StftP p, int B, int, hipStream_t s) {
+    hipLaunchKernelGGL(stft_r8_k, dim3(cdiv(p.n_frames, FPG), B), dim3(256), 0, s, p);
+    return FT_OK;
+}
+
+int launch_istft_r8(const IstftP& p, int B, int, hipStream_t s) {
+    hipLaunchKernelGGL(istft_r8_k, dim3(cdiv(p.n_out, 16 * p.hop), B), dim3(256), 0, s, p);
+    return FT_OK;
+}
+
+// the entries below are the shared launch path (stft_common.h) at n_fft = win_length = 1024 with hop <= 256
+const StftFamily R8 = {launch_stft_r8, launch_istft_r8, 256, 0};
+
 }  // namespace
+
+// y [B,N] -> any of mel [B,n_mel,T] (needs the CSR filterbank), mag [B,513,T], phase [B,513,T] (both or neither); T = N / hop + 1.
+// n_fft = 1024 (hann window [1024] passed in, any win_length zero-padded by the caller), hop <= 256.
+extern "C" int ft_stft_r8(const float* y, const float* window, const int32_t* band_bin0, const int32_t* band_ptr,
+                          const float* band_w, float* mel, float* mag, float* phase, int B, int N, int hop, int n_mel,
+                          void* stream) {
+    return stft_forward(__func__, R8, y, nullptr, false, window, band_bin0, band_ptr, band_w, mel, mag, phase, B, N, NFFT, hop, NFFT,
+                        n_mel, nullptr, stream);
+}
+
+// The collated batch of the data path (data.py:207-229 pads every mel with zeros to the longest one): y [B,N] zero-padded audio,
+// utterance b holds n_samples[b] samples (device int32) -> mel [B,n_mel,T_out]: frames < n_samples[b] / hop + 1 as ft_stft_r8
+// computes them for that utterance alone (reflection about ITS last sample), zeros beyond.  ONE launch for the batch instead of
+// one per utterance (each ~35 us of latency for <= 862 frames).  T_out >= max_b (n_samples[b] / hop + 1).
+extern "C" int ft_stft_r8_ragged(const float* y, const int32_t* n_samples, const float* window, const int32_t* band_bin0,
+                                 const int32_t* band_ptr, const float* band_w, float* mel, int B, int N, int hop, int n_mel,
+                                 int T_out, void* stream) {
+    return stft_forward(__func__, R8, y, n_samples, true, window, band_bin0, band_ptr, band_w, mel, nullptr, nullptr, B, N, NFFT, hop,
+                        NFFT, n_mel, &T_out, stream);
+}
+
+// The spectrum of a ragged batch (the analysis step of griffin_lim_ragged): y [B,N], utterance b holds n_samples[b] samples
+// (device int32) -> mag (NULL = skip the store: Griffin-Lim keeps the phase only) and phase [B,513,T_out], T_out = N / hop + 1:
+// frames < n_samples[b] / hop + 1 exactly as ft_stft_r8 computes them for y[b, :n_samples[b]] alone (reflection about ITS last
+// sample, so the samples behind it are never read), zeros beyond in every output that is written.  ONE launch for the batch.
+extern "C" int ft_stft_r8_ragged_phase(const float* y, const int32_t* n_samples, const float* window, float* mag, float* phase,
+                                       int B, int N, int hop, void* stream) {
+    return stft_forward(__func__, R8, y, n_samples, true, window, nullptr, nullptr, nullptr, nullptr, mag, phase, B, N, NFFT, hop,
+                        NFFT, 0, nullptr, stream);
+}
 
 // (mag, phase) [B,513,T] -> y [B, hop (T-1)]: STFT.inverse (audio_processing.py:237-263) for n_fft = 1024, hop <= 256;
 // window: hann [1024] (win_length zero-padded by the caller), as ft_stft_r8.
 extern "C" int ft_istft_r8(const float* mag, const float* phase, const float* window, float* y, int B, int T, int hop,
                            void* stream) {
-    FT_CHECK_ARG(mag && phase && window && y);
-    FT_CHECK_ARG(B >= 1 && B <= 65535 && hop >= 1 && hop <= 256 && T >= 2);
-    FT_CHECK_ARG((int64_t)hop * (T - 1) <= INT32_MAX - 2 * NFFT);
-    const int n_out = hop * (T - 1);
-    IstftP p{mag, phase, window, y, T, hop, n_out, nullptr};
-    hipLaunchKernelGGL(istft_r8_k, dim3(cdiv(n_out, 16 * hop), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
-    FT_CHECK_LAUNCH();
-    return FT_OK;
+    return stft_inverse(__func__, R8, mag, phase, nullptr, false, window, y, B, T, NFFT, hop, NFFT, stream);
 }
 
 // The inverse of a ragged batch (the synthesis step of griffin_lim_ragged): (mag, phase) [B,513,T] with row stride T, utterance b
@@ -469,12 +417,5 @@ extern "C" int ft_istft_r8(const float* mag, const float* phase, const float* wi
 // never read.  ONE launch for the batch, no atomics, launch-independent.  Same preconditions as ft_istft_r8.
 extern "C" int ft_istft_r8_ragged(const float* mag, const float* phase, const int32_t* n_frames, const float* window, float* y,
                                   int B, int T, int hop, void* stream) {
-    FT_CHECK_ARG(mag && phase && n_frames && window && y);
-    FT_CHECK_ARG(B >= 1 && B <= 65535 && hop >= 1 && hop <= 256 && T >= 2);
-    FT_CHECK_ARG((int64_t)hop * (T - 1) <= INT32_MAX - 2 * NFFT);
-    const int n_out = hop * (T - 1);
-    IstftP p{mag, phase, window, y, T, hop, n_out, n_frames};
-    hipLaunchKernelGGL(istft_r8_k, dim3(cdiv(n_out, 16 * hop), B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p);
-    FT_CHECK_LAUNCH();
-    return FT_OK;
+    return stft_inverse(__func__, R8, mag, phase, n_frames, true, window, y, B, T, NFFT, hop, NFFT, stream);
 }

@@ -28,9 +28,12 @@ class DeferredMel:
     """The `mel` slot of a collated batch when the items carry AUDIO instead of spectrograms (drop-in `Data` below).
     The reference computes every mel on the host, one item at a time, inside the single DataLoader worker
     (data.py:149-155, train.py:77); a forked worker cannot touch the GPU, so the worker ships the padded audio and the
-    spectrogram is computed by the HIP front end (ft_stft_mel) when the training loop calls `.cuda()` on the slot
-    (train.py:286) -- the one call the reference makes on it.  Result: [B, n_mel, T_max] fp32 on the device, zero beyond
-    each utterance's frames, exactly what DataCollate's zero padding produces (data.py:215-229)."""
+    spectrogram is computed by the HIP front end when the training loop calls `.cuda()` on the slot (train.py:286) -- the
+    one call the reference makes on it: ONE launch for the batch, ft_stft_r8_ragged at n_fft 1024 with hop <= 256 and
+    ft_stft_pow2_ragged at the other power-of-two settings; only outside both (another n_fft, more than 128 mel
+    channels, an utterance no longer than n_fft / 2) one ft_stft_mel launch per utterance.  Result: [B, n_mel, T_max]
+    fp32 on the device, zero beyond each utterance's frames, exactly what DataCollate's zero padding produces
+    (data.py:215-229)."""
 
     def __init__(self, audio, n_samples, stft_args, max_t=None, source_rates=None):
         # max_t: the padded frame count DataCollate uses for every slot of the batch (rounded up to a multiple of

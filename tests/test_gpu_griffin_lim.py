@@ -1,6 +1,6 @@
 """The synthesis side of the audio front end on the MI355X: STFT.inverse (ft_istft_r8), STFT.forward, griffin_lim (ft_stft_r8 +
-ft_istft_r8 in a loop) and TacotronSTFT.mel_to_magnitude / mel_to_audio (ft_gemm + Griffin-Lim), against a float64 restatement
-of the reference's formulas (audio_processing.py:7-75, 237-270) that lives in this file, and against the REAL reference's
+ft_istft_r8 in a loop) and TacotronSTFT.mel_to_magnitude / mel_to_audio (ft_gemm + Griffin-Lim), against the float64 restatement
+of the reference's formulas (audio_processing.py:7-75, 237-270) in tests/stft_ref64.py, and against the REAL reference's
 outputs in tests/golden/griffin_lim.pt (tests/golden/make_golden_gl.py).  The fixture stores no inputs: they are rebuilt
 here from the same seeds (`random_spectrum`, `magnitudes32`), and the magnitudes are checked against its fingerprint.
 
@@ -15,20 +15,12 @@ import torch
 
 import audio_processing
 from flowtron_amd import _lib as L
+from stft_ref64 import TINY32, griffin_lim64, hann64, istft64, rel_l2, start_angles, stft64, wss64
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "griffin_lim.pt")
 EPS32 = float(np.finfo(np.float32).eps)
-TINY32 = float(np.finfo(np.float32).tiny)
-
-
-# ---- float64 restatement ------------------------------------------------------------------------------------------------------
-def hann64(win_length, n_fft=1024):
-    w = np.zeros(n_fft)
-    lp = (n_fft - win_length) // 2
-    w[lp:lp + win_length] = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(win_length) / win_length)
-    return w
 
 
 def ola(frames, hop):
@@ -40,31 +32,6 @@ def ola(frames, hop):
     return out
 
 
-def wss64(T, hop, win_length):
-    w = hann64(win_length)
-    return ola(np.repeat((w * w)[None, :, None], T, axis=2), hop)[0]
-
-
-def istft64(M, P, hop, win_length):
-    B, _, T = M.shape
-    w = hann64(win_length)
-    fr = np.fft.irfft(np.asarray(M, np.float64) * np.exp(1j * np.asarray(P, np.float64)), n=1024, axis=1) * w[None, :, None]
-    out = ola(fr, hop)
-    wss = wss64(T, hop, win_length)
-    nz = wss > TINY32
-    out[:, nz] /= wss[nz]
-    return out[:, 512:out.shape[1] - 512]
-
-
-def transform64(y, hop, win_length):
-    B, N = y.shape
-    w = hann64(win_length)
-    yp = np.pad(np.asarray(y, np.float64), ((0, 0), (512, 512)), mode="reflect")
-    idx = np.arange(N // hop + 1)[:, None] * hop + np.arange(1024)[None, :]
-    X = np.fft.rfft(yp[:, idx] * w, axis=2).transpose(0, 2, 1)
-    return np.abs(X), np.angle(X)
-
-
 def random_spectrum(seed, B, T):
     rs = np.random.RandomState(seed)
     M = rs.uniform(0.0, 2.0, (B, 513, T)).astype(np.float32)
@@ -74,28 +41,11 @@ def random_spectrum(seed, B, T):
 
 def magnitudes32(y, hop=256, win_length=1024):
     """Griffin-Lim input of the fixture's cases: |STFT(y)| in float64, rounded once to float32."""
-    return transform64(np.asarray(y, np.float64), hop, win_length)[0].astype(np.float32)
-
-
-def start_angles(shape, seed=0):
-    np.random.seed(seed)
-    return np.angle(np.exp(2j * np.pi * np.random.rand(*shape))).astype(np.float32)
-
-
-def griffin_lim64(M, angles, n_iters, hop=256, win_length=1024):
-    y = istft64(M, angles, hop, win_length)
-    for _ in range(n_iters):
-        y = istft64(M, transform64(y, hop, win_length)[1], hop, win_length)
-    return y
-
-
-def rel_l2(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / np.linalg.norm(b))
+    return np.abs(stft64(np.asarray(y, np.float64), 1024, hop, win_length)).astype(np.float32)
 
 
 def spectral_convergence(y, M, hop=256, win_length=1024):
-    return float(np.linalg.norm(transform64(y, hop, win_length)[0] - M) / np.linalg.norm(M))
+    return float(np.linalg.norm(np.abs(stft64(y, 1024, hop, win_length)) - M) / np.linalg.norm(M))
 
 
 def inverse_bound(M, hop, win_length):
@@ -110,9 +60,9 @@ def inverse_bound(M, hop, win_length):
     B, _, T = M.shape
     M = np.asarray(M, np.float64)
     A = (2 * M.sum(axis=1) - M[:, 0] - M[:, 512]) / 1024                  # [B, T]
-    w = hann64(win_length)
+    w = hann64(win_length, 1024)
     env = ola(np.abs(w)[None, :, None] * A[:, None, :], hop)
-    wss = wss64(T, hop, win_length)
+    wss = wss64(T, 1024, hop, win_length)
     nz = wss > TINY32
     env[:, nz] /= wss[nz]
     return 8 * EPS32 * 10 * env[:, 512:env.shape[1] - 512]
@@ -124,7 +74,7 @@ def check_inverse(M, P, hop, win_length, what):
     B, _, T = M.shape
     assert y.shape == (B, 1, hop * (T - 1)), (what, y.shape)
     y = y[:, 0].cpu().double().numpy()
-    y64 = istft64(M, P, hop, win_length)
+    y64 = istft64(M, P, 1024, hop, win_length)[0]
     bound = inverse_bound(M, hop, win_length) + 8 * EPS32 * np.abs(y64)
     ratio = np.abs(y - y64) / bound
     print("%s: max |gpu - f64| / bound = %.3g, rel L2 %.2e" % (what, ratio.max(), rel_l2(y, y64)))
@@ -201,7 +151,7 @@ def _gl_case(golden, name, n):
     stft = audio_processing.STFT(1024, 256, 1024).cuda()
     np.random.seed(0)
     y = audio_processing.griffin_lim(torch.from_numpy(M).cuda(), stft, n).cpu()
-    y64 = griffin_lim64(M, start_angles(M.shape), n)
+    y64 = griffin_lim64(M, start_angles(M.shape), n, 1024, 256, 1024)
     ref = g["y"][n] if name == "gl_41" else g["y"]                      # every stride-th sample of the reference's output
     dev = g["dev64"][n] if name == "gl_41" else g["dev64"]
     return M, y.numpy(), y64, ref.numpy(), dev, g["stride"]
@@ -266,7 +216,7 @@ def test_mel_round_trip():
         return float(np.abs(tst.mel_spectrogram(audio).cpu().double().numpy() - mel_np).mean())
 
     def logmel_err64(audio):
-        m64 = np.log(np.maximum(np.einsum("mk,bkt->bmt", fb, transform64(audio, 256, 1024)[0]), 1e-5))
+        m64 = np.log(np.maximum(np.einsum("mk,bkt->bmt", fb, np.abs(stft64(audio, 1024, 256, 1024))), 1e-5))
         return float(np.abs(m64 - mel_np).mean())
 
     errs, errs64 = {}, {}
@@ -276,7 +226,7 @@ def test_mel_round_trip():
         assert audio.shape == (1, 256 * (mel.shape[2] - 1))
         errs[n] = logmel_err(audio)
         M64 = np.maximum(np.einsum("km,bmt->bkt", pinv, np.exp(mel_np)), 0)
-        errs64[n] = logmel_err64(griffin_lim64(M64, start_angles(M64.shape), n))
+        errs64[n] = logmel_err64(griffin_lim64(M64, start_angles(M64.shape), n, 1024, 256, 1024))
     print("log-mel mean |error|: n_iters 0 %.4f, 60 %.4f (float64 pipeline %.4f, %.4f)" % (errs[0], errs[60], errs64[0], errs64[60]))
     assert errs[60] < errs[0]
     assert abs(errs[60] / errs64[60] - 1) < 0.05

@@ -12,6 +12,7 @@ import torch
 import audio_processing
 import resample_case as C
 import resample_ref64 as R
+from call_count import count_calls
 from flowtron_amd import _lib as L
 from flowtron_amd import audio as A
 from flowtron_amd.data import Data, DataCollate
@@ -20,19 +21,6 @@ pytestmark = pytest.mark.gpu
 
 PAIRS = [(24000, 22050), (16000, 22050), (44100, 22050), (48000, 8000), (8000, 48000), (44100, 48000)]
 EPS = 2.0 ** -24
-
-
-def count_calls(monkeypatch, names):
-    lib = L.lib()
-    calls = {n: 0 for n in names}
-    for name in names:
-        fn = getattr(lib, name)
-
-        def shim(*a, _fn=fn, _n=name):
-            calls[_n] += 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, name, shim)
-    return calls
 
 
 def check_against_float64(x, orig, new):

@@ -1,7 +1,7 @@
 """The audio front end at every power-of-two analysis size on the MI355X: STFT.transform / inverse (ft_stft_pow2 / ft_istft_pow2),
 the mel spectrogram, its ragged one-launch form (ft_stft_pow2_ragged), DeferredMel, griffin_lim and mel_to_audio at n_fft =
-256 .. 4096 and hops the 1024 kernels do not take, against a float64 restatement of the reference's formulas
-(audio_processing.py:7-75, 96-270) that lives in this file, and against the REAL reference's outputs in tests/golden/stft_pow2.pt
+256 .. 4096 and hops the 1024 kernels do not take, against the float64 restatement of the reference's formulas
+(audio_processing.py:7-75, 96-270) in tests/stft_ref64.py, and against the REAL reference's outputs in tests/golden/stft_pow2.pt
 (tests/golden/make_golden_stft_pow2.py).  The 1024 / hop <= 256 setting keeps its own kernels (checked by counting calls).
 
 Measured deviations from the float64 restatement are printed by every test (pytest -s)."""
@@ -12,53 +12,13 @@ import pytest
 import torch
 
 import audio_processing
+from call_count import count_calls
 from flowtron_amd import _lib as L
+from stft_ref64 import TINY32, griffin_lim64, istft64, rel_l2, start_angles, stft64
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stft_pow2.pt")
-TINY32 = float(np.finfo(np.float32).tiny)
-
-
-# ---- float64 restatement ------------------------------------------------------------------------------------------------------
-def hann64(win_length, n_fft):
-    w = np.zeros(n_fft)
-    lp = (n_fft - win_length) // 2
-    w[lp:lp + win_length] = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(win_length) / win_length)
-    return w
-
-
-def stft64(y, n_fft, hop, win_length):
-    """complex [B, n_fft/2+1, N // hop + 1]: reflect pad by n_fft/2, hann window, rfft."""
-    B, N = y.shape
-    w = hann64(win_length, n_fft)
-    yp = np.pad(np.asarray(y, np.float64), ((0, 0), (n_fft // 2, n_fft // 2)), mode="reflect")
-    idx = np.arange(N // hop + 1)[:, None] * hop + np.arange(n_fft)[None, :]
-    return np.fft.rfft(yp[:, idx] * w, axis=2).transpose(0, 2, 1)
-
-
-def wss64(T, n_fft, hop, win_length):
-    w2 = hann64(win_length, n_fft) ** 2
-    out = np.zeros(n_fft + hop * (T - 1))
-    for t in range(T):
-        out[t * hop:t * hop + n_fft] += w2
-    return out
-
-
-def istft64(M, P, n_fft, hop, win_length):
-    """(y [B, hop (T-1)], wss over the same samples)."""
-    B, _, T = M.shape
-    w = hann64(win_length, n_fft)
-    fr = np.fft.irfft(np.asarray(M, np.float64) * np.exp(1j * np.asarray(P, np.float64)), n=n_fft, axis=1) * w[None, :, None]
-    n = n_fft + hop * (T - 1)
-    out = np.zeros((B, n))
-    for t in range(T):
-        out[:, t * hop:t * hop + n_fft] += fr[:, :, t]
-    wss = wss64(T, n_fft, hop, win_length)
-    nz = wss > TINY32
-    out[:, nz] /= wss[nz]
-    h = n_fft // 2
-    return out[:, h:n - h], wss[h:n - h]
 
 
 def mel64(y, tst):
@@ -67,39 +27,9 @@ def mel64(y, tst):
     return np.log(np.maximum(np.einsum("mk,bkt->bmt", tst.mel_basis.cpu().double().numpy(), np.abs(X)), 1e-5))
 
 
-def griffin_lim64(M, angles, n_iters, n_fft, hop, win_length):
-    y = istft64(M, angles, n_fft, hop, win_length)[0]
-    for _ in range(n_iters):
-        y = istft64(M, np.angle(stft64(y, n_fft, hop, win_length)), n_fft, hop, win_length)[0]
-    return y
-
-
-def start_angles(shape, seed=0):
-    np.random.seed(seed)
-    return np.angle(np.exp(2j * np.pi * np.random.rand(*shape))).astype(np.float32)
-
-
-def rel_l2(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / np.linalg.norm(b))
-
-
 def audio(B, N, seed):
     from oracle import synth
     return torch.stack([synth.make_audio(N, seed=seed + i) for i in range(B)])
-
-
-def count_calls(monkeypatch, names):
-    lib = L.lib()
-    calls = {n: 0 for n in names}
-    for name in names:
-        fn = getattr(lib, name)
-
-        def shim(*a, _fn=fn, _n=name):
-            calls[_n] += 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, name, shim)
-    return calls
 
 
 # (n_fft, hop, win_length, B, N): every power-of-two size, 1024 at hops above 256, win_length < n_fft with an odd gap,

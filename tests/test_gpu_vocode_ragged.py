@@ -19,11 +19,11 @@ import pytest
 import torch
 
 import audio_processing
-from flowtron_amd import _lib as L
+from call_count import count_calls
+from stft_ref64 import TINY32, istft64
 
 pytestmark = pytest.mark.gpu
 
-TINY32 = float(np.finfo(np.float32).tiny)
 INV_BOUND = 1e-6                      # relative L2 against float64: the bound of test_gpu_stft_pow2.py for the dense inverse
 
 # (n_fft, hop, win_length) -> (T, n_frames)
@@ -55,44 +55,6 @@ def spectrum(key, B, T, seed, lens=None):
             M[b, :, n:] = np.nan
             P[b, :, n:] = np.nan
     return torch.from_numpy(M), torch.from_numpy(P)
-
-
-def count_calls(monkeypatch, names):
-    lib = L.lib()
-    calls = {n: 0 for n in names}
-    for name in names:
-        fn = getattr(lib, name)
-
-        def shim(*a, _fn=fn, _n=name):
-            calls[_n] += 1
-            return _fn(*a)
-        monkeypatch.setattr(lib, name, shim)
-    return calls
-
-
-# ---- float64 restatement of STFT.inverse (audio_processing.py:237-263) -----------------------------------------------------------
-def hann64(win_length, n_fft):
-    w = np.zeros(n_fft)
-    lp = (n_fft - win_length) // 2
-    w[lp:lp + win_length] = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(win_length) / win_length)
-    return w
-
-
-def istft64(M, P, n_fft, hop, win_length):
-    """(y [B, hop (T-1)], wss over the same samples): windowed irfft of every frame, overlap-add, division by the window's
-    sum-square envelope where it is > tiny(float32), n_fft/2 samples cut at both ends."""
-    B, _, T = M.shape
-    w = hann64(win_length, n_fft)
-    fr = np.fft.irfft(np.asarray(M, np.float64) * np.exp(1j * np.asarray(P, np.float64)), n=n_fft, axis=1) * w[None, :, None]
-    n = n_fft + hop * (T - 1)
-    out, wss = np.zeros((B, n)), np.zeros(n)
-    for t in range(T):
-        out[:, t * hop:t * hop + n_fft] += fr[:, :, t]
-        wss[t * hop:t * hop + n_fft] += w ** 2
-    nz = wss > TINY32
-    out[:, nz] /= wss[nz]
-    h = n_fft // 2
-    return out[:, h:n - h], wss[h:n - h]
 
 
 # ---- 1. the inverse equals each utterance alone ---------------------------------------------------------------------------------

@@ -38,7 +38,7 @@ class GemmImgArgs(C.Structure):
                 ("lda", _l), ("ldb", _l), ("ldc", _l), ("a_kmajor", _i), ("b_kmajor", _i),
                 ("alpha", _f), ("beta", _f), ("act", _i), ("flags", _i),
                 ("rowmap", _p), ("rows_dev", _p), ("compact", _i), ("k_shift", _i), ("r1_row", _p), ("r1_col", _p),
-                ("split_work", _p), ("split_work_bytes", _sz)]
+                ("split_work", _p), ("split_work_bytes", _sz), ("a_rows", _p)]
 
 
 class LstmFwdRole(C.Structure):
@@ -102,6 +102,7 @@ SIGNATURES = {
     "ft_bf16_image_table_f16": ([C.POINTER(ImgDesc), _i, _p], _i),
     "ft_bf16_image_split3_f16": ([_p, _l, _l, _l, _p, _i, _p], _i),
     "ft_rowmap_build": ([_p, _p, _p, _i, _i, _p], _i),
+    "ft_chunk_gather_rows": ([_p, _p, _p, _i, _i, _i, _i, _p], _i),
     "ft_bf16_image_rows": ([_p, _l, _l, _l, _p, _p, _p, _p, _p], _i),
     "ft_bf16_image_rows_acc": ([_p, _l, _l, _l, _p, _p, _p, _p, _p], _i),
     "ft_bf16_image_rows_into": ([_p, _l, _l, _l, _p, _l, _l, _l, _p, _p, _p], _i),

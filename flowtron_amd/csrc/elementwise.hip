@@ -415,6 +415,25 @@ __global__ void rowmap_k(const int* __restrict__ lens, int* __restrict__ rowmap,
     }
 }
 
+// Row lists of ONE time chunk [t0, t1) of the batch (ft_chunk_gather_rows): the chunk's compact rows are those of rowmap_k over the
+// chunk's own lengths lk_b = clamp(lens[b] - t0, 0, t1 - t0); compact row i = (t, b), t < lk_b, reads row off_b + t0 + t of the WHOLE
+// sequence's compact image (off_b = sum of (len + 1) of the utterances before b: rowmap_k's offsets) and goes to row t * B + b of the
+// chunk's time-major output.  A separator row of the chunk has no row of its own in that image that is written before the sequence's
+// first window has run: its output is dropped (-1), and it reads a valid row of the chunk (its utterance's last one, else a neighbour's).
+__global__ void chunk_rows_k(const int* __restrict__ lens, int* __restrict__ a_rows, int* __restrict__ rowmap, int T, int B, int t0, int t1) {
+    const int b = blockIdx.x, w = t1 - t0;
+    int off = 0, offc = 0, near = -1, off_b = 0, offc_b = 0, lk_b = 0;
+    for (int i = 0; i < B; ++i) {
+        int l = lens[i]; l = l < 0 ? 0 : (l > T ? T : l);
+        int lk = l - t0; lk = lk < 0 ? 0 : (lk > w ? w : lk);
+        if (i == b) { off_b = off; offc_b = offc; lk_b = lk; }
+        if (lk > 0 && (i <= b || near < 0)) near = off + t0 + lk - 1;
+        off += l + 1; offc += lk + 1;
+    }
+    for (int t = threadIdx.x; t < lk_b; t += blockDim.x) { a_rows[offc_b + t] = off_b + t0 + t; rowmap[offc_b + t] = t * B + b; }
+    if (threadIdx.x == 0) { a_rows[offc_b + lk_b] = near < 0 ? 0 : near; rowmap[offc_b + lk_b] = -1; }
+}
+
 // grid (T*B rows, cols/1024 chunks): padded rows t > lens[b] only
 __global__ void pad_fill_k(float* __restrict__ y, long ld, int cols, const int* __restrict__ lens, int T, int B, int mode) {
     const int row = blockIdx.x, t = row / B, b = row % B;
@@ -720,6 +739,12 @@ extern "C" int ft_radam_step_dev(float* p, const float* g, float* m, float* v, i
 extern "C" int ft_rowmap_build(const int32_t* lens, int32_t* rowmap, int32_t* rows_dev, int T, int B, void* stream) {
     FT_CHECK_ARG(lens && rowmap && rows_dev && T >= 1 && B >= 1 && (int64_t)T * B + B < (1ll << 31));
     hipLaunchKernelGGL(rowmap_k, dim3(B), dim3(256), 0, ST(stream), lens, rowmap, rows_dev, T, B);
+    FT_CHECK_LAUNCH();
+    return FT_OK;
+}
+extern "C" int ft_chunk_gather_rows(const int32_t* lens, int32_t* a_rows, int32_t* rowmap, int T, int B, int t0, int t1, void* stream) {
+    FT_CHECK_ARG(lens && a_rows && rowmap && T >= 1 && B >= 1 && t0 >= 0 && t0 < t1 && t1 <= T && (int64_t)T * B + B < (1ll << 31));
+    hipLaunchKernelGGL(chunk_rows_k, dim3(B), dim3(256), 0, ST(stream), lens, a_rows, rowmap, T, B, t0, t1);
     FT_CHECK_LAUNCH();
     return FT_OK;
 }

@@ -280,6 +280,8 @@ struct BfP {
     // FT_GEMM_C16: C is a 16-BIT matrix of this build's operand format (ldc in 16-bit elements): the fp32 result (+ bias) is rounded
     // once in the epilogue -- the gx rows a persistent recurrence reads (half the bytes written here and read there)
     int c16;
+    // row gather of the A operand (ft_gemm_img_args.a_rows; the GA instantiations): tile row m reads image row a_rows[m]
+    const int* a_rows;
 };
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -368,7 +370,9 @@ __device__ __forceinline__ void tr_wait(bf16x4 (&t)[8], bf16x4 (&u)[8]) {
 // profiles/r06_dma_stream_probe.log): 16-row x 64 B pieces stream 16.5 TB/s into the LDS of the 256 CUs at 4 workgroups per CU,
 // 8-row x 128 B pieces 21 TB/s at 2 per CU (24.5 at 4).  LDS image: 128-byte rows, the 16-byte chunk c of row r stored at
 // c ^ ((r >> 1) & 7) (swizzle on the DMA source, as gemm_bf16_p256_k); the fragment of k-step ks is one ds_read_b128.
-template <int RT>
+// GA (row gather): the lane's NS pieces start at image rows looked up ONCE in a row list -- tile row m reads image row rows[min(m, last)]
+// -- and it keeps their NS sources (chunk swizzle folded in) instead of src0 + g ld8; the stages and the LDS image are the same.
+template <int RT, bool GA = false>
 struct Operand64 {
     static constexpr int NS = RT / 32;         // pieces per wave and stage (the wave stages rows 8 NS wave .. + 8 NS - 1)
     static constexpr int WT = RT / 32;         // 16-row fragments per wave tile
@@ -377,6 +381,7 @@ struct Operand64 {
     int dst0;                                  // byte offset of piece 0 inside the operand's stage buffer
     int xodd;                                  // element offset that turns the even pieces' chunk into the odd pieces' (c ^ 4)
     int roff;
+    const unsigned short* srcg[GA ? NS : 1];   // GA: this lane's source of piece g (k = 0)
     __device__ __forceinline__ void init(const unsigned short* img, long ld, int r0, int wave, int lane, int wsel) {
         const int li = lane & 15, kg = lane >> 4;
         const int prow = lane >> 3, pch = lane & 7;
@@ -387,11 +392,28 @@ struct Operand64 {
         dst0 = wave * NS * 1024;
         roff = (wsel * (RT / 2) + li) * 128 + ((kg ^ (li >> 1)) << 4);
     }
+    // GA: rows = the row list, last = the index of its last entry (tile rows beyond it read that entry's row: their outputs are dropped)
+    __device__ __forceinline__ void init_rows(const unsigned short* img, long ld, int r0, int wave, int lane, int wsel, const int* rows, int last) {
+        const int li = lane & 15, kg = lane >> 4;
+        const int prow = lane >> 3, pch = lane & 7;
+        const int c = pch ^ (prow >> 1);
+#pragma unroll
+        for (int g = 0; g < NS; ++g) {
+            const int m = r0 + (wave * NS + g) * 8 + prow;
+            srcg[g] = img + (size_t)rows[m < last ? m : last] * ld + ((g & 1) ? (c ^ 4) : c) * 8;
+        }
+        dst0 = wave * NS * 1024;
+        roff = (wsel * (RT / 2) + li) * 128 + ((kg ^ (li >> 1)) << 4);
+    }
     __device__ __forceinline__ void issue(unsigned char* sbuf, int t) const {       // t counts 64-wide stages
 #pragma unroll
-        for (int g = 0; g < NS; ++g)
-            __builtin_amdgcn_global_load_lds((glb_void*)(src0 + (size_t)t * 64 + (size_t)g * ld8 + ((g & 1) ? xodd : 0)),
-                                             (lds_void*)(sbuf + dst0 + g * 1024), 16, 0, 0);
+        for (int g = 0; g < NS; ++g) {
+            if constexpr (GA)
+                __builtin_amdgcn_global_load_lds((glb_void*)(srcg[g] + (size_t)t * 64), (lds_void*)(sbuf + dst0 + g * 1024), 16, 0, 0);
+            else
+                __builtin_amdgcn_global_load_lds((glb_void*)(src0 + (size_t)t * 64 + (size_t)g * ld8 + ((g & 1) ? xodd : 0)),
+                                                 (lds_void*)(sbuf + dst0 + g * 1024), 16, 0, 0);
+        }
     }
     __device__ __forceinline__ bf16x8 frag(const unsigned char* sbuf, int i, int ks) const {
         return *reinterpret_cast<const bf16x8*>(sbuf + ((roff + (i << 11)) ^ (ks << 6)));
@@ -403,9 +425,11 @@ struct Operand64 {
 // KS = 64: 64-wide k stages (two MFMA k-steps per stage; the k-contiguous operands as Operand64, a k-major operand as two of its
 // 32-wide sub-stages side by side); t0 / t1 / ksteps keep counting 32-wide steps (t0 even).  SB: a single 32 KiB LDS buffer, 4
 // workgroups per CU (with two buffers the stage is 64 KiB and only 2 workgroups fit a CU: slower than 32-wide stages at K = 1024)
-template <bool AKM, bool BKM, bool SPLIT, int RTA, int KS = 32, bool SB = false>
+// GA: the A operand's rows are gathered through p.a_rows (compact == 1; the single-buffer form with a k-contiguous A only)
+template <bool AKM, bool BKM, bool SPLIT, int RTA, int KS = 32, bool SB = false, bool GA = false>
 __global__ __launch_bounds__(256, SB ? 4 : (RTA == 256 || KS == 64) ? 2 : 4) void gemm_bf16_k(BfP p) {
     static_assert(!SB || (KS == 64 && RTA == 128 && !SPLIT), "single-buffer form: 128 x 128 x 64 store kernels");
+    static_assert(!GA || (SB && !AKM), "row gather: the single-buffer form, k-contiguous A");
     constexpr int KQ = KS / 32;                        // MFMA k-steps per stage
     constexpr int OPA = RTA * 64 * KQ, OPB = 8192 * KQ;     // bytes per operand per stage
     constexpr int TI = RTA / 32;                       // 16-row fragments of the wave tile along M
@@ -471,9 +495,10 @@ __global__ __launch_bounds__(256, SB ? 4 : (RTA == 256 || KS == 64) ? 2 : 4) voi
 
     Operand<AKM, RTA> oa;
     Operand<BKM, 128> ob;
-    Operand64<RTA> oa64;
+    Operand64<RTA, GA> oa64;
     Operand64<128> ob64;
-    if constexpr (KS == 64 && !AKM) oa64.init(p.A, p.lda, m0, wave, lane, wm); else oa.init(p.A, p.lda, m0, wave, lane, wm);
+    if constexpr (GA) oa64.init_rows(p.A, p.lda, m0, wave, lane, wm, p.a_rows, rows_lim - 1);
+    else if constexpr (KS == 64 && !AKM) oa64.init(p.A, p.lda, m0, wave, lane, wm); else oa.init(p.A, p.lda, m0, wave, lane, wm);
     if constexpr (KS == 64 && !BKM) ob64.init(p.B, p.ldb, n0, wave, lane, wn); else ob.init(p.B, p.ldb, n0, wave, lane, wn);
 
     // !SPLIT: acc[i][j] holds C^T: lane (li, kg), register r  <->  C[m = i*16 + li][n = j*16 + kg*4 + r]  (operands swapped
@@ -643,6 +668,9 @@ void launch_s(const BfP& p, dim3 grid, bool big, bool wide, hipStream_t st) {
     } else {
         if (atomics) hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, true, 128>), grid, dim3(256), 0, st, p);
         else if constexpr (!(AKM && BKM)) {
+            if constexpr (!AKM) {
+                if (wide && p.a_rows) { hipLaunchKernelGGL((gemm_bf16_k<false, BKM, false, 128, 64, true, true>), grid, dim3(256), 0, st, p); return; }
+            }
             if (wide) hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, false, 128, 64, true>), grid, dim3(256), 0, st, p);
             else hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, false, 128>), grid, dim3(256), 0, st, p);
         } else hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, false, 128>), grid, dim3(256), 0, st, p);
@@ -701,8 +729,10 @@ long plan_slices(int M, int N, int K, bool can_split, int compact, bool* big_out
 int run_images(const unsigned short* A, long lda, int a_km, const unsigned short* B, long ldb, int b_km, float* C, long ldc,
                const float* bias, int M, int N, int K, float alpha, float beta, int act, int flags, hipStream_t st,
                const int* rowmap = nullptr, const int* rows_dev = nullptr, int compact = 0, int k_shift = 0,
-               const float* r1row = nullptr, const float* r1col = nullptr, float* split_work = nullptr, size_t split_work_bytes = 0) {
+               const float* r1row = nullptr, const float* r1col = nullptr, float* split_work = nullptr, size_t split_work_bytes = 0,
+               const int* a_rows = nullptr) {
     BfP p;
+    p.a_rows = a_rows;
     p.A = A; p.B = B; p.C = C; p.bias = bias;
     p.M = M; p.N = N; p.nk = cdiv(K, 32); p.lda = lda; p.ldb = ldb; p.ldc = ldc;
     p.alpha = alpha; p.beta = beta; p.act = act;
@@ -739,6 +769,8 @@ int run_images(const unsigned short* A, long lda, int a_km, const unsigned short
     p.ksteps = cdiv(p.nk, s);
     if (wide && (p.ksteps & 1)) ++p.ksteps;            // (k-slices of whole 64-wide stages)
     p.splits = cdiv(p.nk, p.ksteps);
+    if (a_rows && (!wide || p.splits != 1))
+        return ft_fail(FT_EINVAL, "ft_gemm_img: a_rows is read by the 64-wide single-buffer kernel only (FT_GEMM_BF16_WIDE=0 / FT_GEMM_BF16_TILE=256 exclude it)");
     const bool det_on = det && p.splits > 1;
     if (det_on) {
         p.C = split_work; p.ldc = N; p.c_slice = (long)M * N; p.bias = nullptr;
@@ -1017,10 +1049,12 @@ extern "C" int FT_OPNAME(ft_gemm_img)(const ft_gemm_img_args* a, void* stream) {
     FT_CHECK_ARG(a->compact >= 0 && a->compact <= 2 && (a->compact == 0 || a->rows_dev) && (a->compact != 1 || a->rowmap));
     FT_CHECK_ARG(a->k_shift >= 0 && (a->compact == 2 || a->k_shift == 0));
     FT_CHECK_ARG((a->r1_row == nullptr) == (a->r1_col == nullptr));
+    // row gather of A: the 64-wide single-buffer store kernel's conditions
+    FT_CHECK_ARG(a->a_rows == nullptr || (a->compact == 1 && a->a_kmajor == 0 && !(a->flags & (FT_GEMM_SPLITK | FT_GEMM_SPLITK_DET)) && a->K % 64 == 0));
     return run_images(reinterpret_cast<const unsigned short*>(a->A), a->lda, a->a_kmajor, reinterpret_cast<const unsigned short*>(a->B),
                       a->ldb, a->b_kmajor, a->C, a->ldc, a->bias, a->M, a->N, a->K, a->alpha, a->beta, a->act, a->flags,
                       reinterpret_cast<hipStream_t>(stream), a->rowmap, a->rows_dev, a->compact, a->k_shift, a->r1_row, a->r1_col,
-                      reinterpret_cast<float*>(a->split_work), a->split_work_bytes);
+                      reinterpret_cast<float*>(a->split_work), a->split_work_bytes, a->a_rows);
 }
 
 // compact image: image row i = source row rowmap[i] (i < *rows_dev; -1 = zero row); buffer sized for cap_rows

@@ -57,7 +57,7 @@ class RowMap:
     pack_padded_sequence, flowtron.py:689-694): compact rows are batch-major, utterance b = its valid frames + ONE separator
     (its first padded frame, or a zero row when it has none).  Built on the device from the int32 length vector -- no host
     sync; `cap` = T*B + B is the capacity images and grids are sized for, `rows` the device-side row count."""
-    __slots__ = ("T", "B", "cap", "lens", "map", "rows")
+    __slots__ = ("T", "B", "cap", "lens", "map", "rows", "gather")
 
     def __init__(self, lens32, T, B):
         L.require_cuda(lens32)
@@ -307,11 +307,12 @@ def images_apply(mode, M, N, K):
 
 
 def gemm_img(A, a_km, a_ptr, B, b_km, b_ptr, Cm, M, N, K, ldc, bias=None, act=L.ACT_NONE, alpha=1.0, beta=0.0, splitk=False,
-             rowmap=None, compact=0, k_shift=0, rank1=None, c16=False):
+             rowmap=None, compact=0, k_shift=0, rank1=None, c16=False, a_rows=None):
     """C[M,N] = act(alpha * A.B + beta*C + bias) from images.  a_ptr / b_ptr: A.ptr(...) / B.ptr(...) (may point inside).
     rowmap + compact: 1 = M runs over the map's compact rows (pass M = rowmap.cap), C rows are scattered through the map;
     2 = the reduction runs over compact rows (pass K = rowmap.cap; k_shift = a row shift already applied to a_ptr).
-    rank1 = (r [C rows] fp32, c_ptr -> N floats): C[row][col] += r[row] * c[col] in the epilogue (row = the output row)."""
+    rank1 = (r [C rows] fp32, c_ptr -> N floats): C[row][col] += r[row] * c[col] in the epilogue (row = the output row).
+    a_rows (int32 device list, compact = 1): compact row m reads row a_rows[m] of A's image instead of row m."""
     L.require_cuda(Cm, bias)
     flags, work, need = (L.GEMM_SPLITK if splitk else 0), None, 0
     if splitk == "det":
@@ -327,7 +328,7 @@ def gemm_img(A, a_km, a_ptr, B, b_km, b_ptr, Cm, M, N, K, ldc, bias=None, act=L.
                       L.ptr(rowmap.map) if rowmap is not None else None, L.ptr(rowmap.rows) if rowmap is not None else None,
                       int(compact) if rowmap is not None else 0, int(k_shift),
                       L.ptr(rank1[0]) if rank1 is not None else None, rank1[1] if rank1 is not None else None,
-                      L.ptr(work), need)
+                      L.ptr(work), need, L.ptr(a_rows) if a_rows is not None else None)
     assert A.fmt == B.fmt, "operand images of different formats"
     L.check(L.op16("ft_gemm_img", A.fmt)(C.byref(a), L.stream()), "ft_gemm_img")
 
@@ -1328,7 +1329,7 @@ def roles_plan(B, backward):
     return out
 
 
-_PAIR_CHUNKS_BWD = int(_os.environ.get("FLOWTRON_LSTM_PAIR_BWD", "0"))   # chunks of the pair's BACKWARD pipeline; 0 = sequential, -1 = as forward
+_PAIR_CHUNKS_BWD = int(_os.environ.get("FLOWTRON_LSTM_PAIR_BWD", "3"))   # chunks of the pair's BACKWARD pipeline; 0 = sequential, -1 = as forward
 _PAIR_CHUNKS = int(_os.environ.get("FLOWTRON_LSTM_PAIR", "6"))       # time chunks of the decoder layer pair pipeline; 0 = one recurrence per launch
 
 
@@ -1367,6 +1368,42 @@ def _chunk_rowmaps(lens, edges, B):
     maps = [RowMap(lk[k], edges[k + 1] - edges[k], B) for k in range(len(edges) - 1)]
     _EDGE_CACHE["last_key"], _EDGE_CACHE["last_lens"], _EDGE_CACHE["last_maps"] = ck, _weakref.ref(lens), maps
     return maps
+
+
+def _gather_gemm_on():
+    """ft_gemm_img's row gather lives in the 64-wide single-buffer kernel alone: under the library's A/B hooks that switch that kernel off
+    (FT_GEMM_BF16_WIDE=0, FT_GEMM_BF16_TILE=256; read per call there, so per call here) the pipeline keeps its fp32-rows form"""
+    def num(name, default):
+        try:
+            return int(_os.environ.get(name, default))
+        except ValueError:
+            return 0                             # (atoi)
+    return num("FT_GEMM_BF16_WIDE", "1") != 0 and num("FT_GEMM_BF16_TILE", "0") != 256
+
+
+def _chunk_gathers(maps, lens, edges):
+    """the chunks' row lists into the whole sequence's batch-major image (ChunkGather; one small launch per chunk), made at the first
+    backward that asks for them (the forward's maps need none unless the backward runs over the same chunks): they ride with the maps,
+    so both flows, and every step that chunks the same `lens` tensor, make them once"""
+    for k, m in enumerate(maps):
+        if getattr(m, "gather", None) is None:
+            m.gather = ChunkGather(lens, m, edges[-1], edges[k], edges[k + 1])
+    return [m.gather for m in maps]
+
+
+class ChunkGather:
+    """Row lists of one time chunk [t0, t1) for a GEMM over the chunk's compact rows that reads them out of the WHOLE sequence's batch-major
+    compact image (csrc: ft_chunk_gather_rows): a_rows[i] = the image row of the chunk's compact row i, map[i] = its row in the chunk's
+    time-major output -- the chunk RowMap's, with the chunk's separator rows dropped (-1): they read a valid row, because the image's own
+    separator rows are only written by the window that holds step 0.  rows / cap are the chunk map's (gemm_img takes this as its rowmap)."""
+    __slots__ = ("cap", "map", "rows", "a_rows")
+
+    def __init__(self, lens32, chunk_map, T, t0, t1):
+        self.cap, self.rows = chunk_map.cap, chunk_map.rows
+        both = torch.empty(2, self.cap, device=lens32.device, dtype=torch.int32)
+        self.a_rows, self.map = both[0], both[1]
+        L.check(L.lib().ft_chunk_gather_rows(L.ptr(lens32), L.ptr(self.a_rows), L.ptr(self.map), int(T), chunk_map.B, int(t0), int(t1), L.stream()),
+                "ft_chunk_gather_rows")
 
 
 class DecoderPairFn(torch.autograd.Function):
@@ -1427,19 +1464,22 @@ class DecoderPairFn(torch.autograd.Function):
         img_only = img_ok and _PERSIST_IMG != "both" and not torch.is_anomaly_enabled()
         w_img = ctx.w_img if ctx.w_img is not None else Bf16Image.of_weight(w_ih1, mode)     # (released by a first backward: retain_graph)
         ctx.w_img = None
-        nb = _PAIR_CHUNKS_BWD if _PAIR_CHUNKS_BWD >= 0 else n
+        nb = min(_PAIR_CHUNKS_BWD, T) if _PAIR_CHUNKS_BWD >= 0 else n      # (at most T windows: none is empty, the edges rise strictly)
         if nb == 0 and rm is not None and img_ok and ctx.needs_input_grad[1] and ctx.needs_input_grad[5]:
             return DecoderPairFn._backward_sequential(ctx, dy1, w_img, img_only)      # (before the pipeline's buffers: four fills less per pass)
+        if nb != n and nb > 0:
+            n = nb
+            edges = _chunk_edges(T, n)
+            rms = _chunk_rowmaps(lens, edges, B)
+        assert all(a < b for a, b in zip(edges, edges[1:])), "empty time window in the pair's backward pipeline"
+        if rm is not None and img_only and ctx.needs_input_grad[1] and ctx.needs_input_grad[5] and T > 1 and _gather_gemm_on():
+            return DecoderPairFn._backward_pipeline_img(ctx, dy1, w_img, n, edges, rms)
         dgx1 = torch.empty(T, B, H4, **f)
         dy0 = torch.empty(T, B, H, **f)
         d_img0 = Bf16Image.empty_rows(H4, rm, mode, dev) if img_ok else None
         dgx0 = None if img_only else torch.empty(T, B, H4, **f)
         sb1 = (torch.zeros(B, H4, **f), torch.zeros(B, H, **f))
         sb0 = (torch.zeros(B, H4, **f), torch.zeros(B, H, **f))
-        if nb != n and nb > 0:
-            n = nb
-            edges = _chunk_edges(T, n)
-            rms = _chunk_rowmaps(lens, edges, B)
         wb0, wb1 = roles_wimg(w_hh0, mode, True), roles_wimg(w_hh1, mode, True)
         for j in range(n + 1):
             c = n - 1 - j                                        # layer 1's chunk in this launch; layer 0 runs chunk c + 1
@@ -1496,7 +1536,9 @@ def _pair_backward_sequential(ctx, dy1, w_img, img_only):
     """DecoderPairFn.backward without the pipeline: layer 1's recurrence, ONE dX GEMM over all valid rows, layer 0's recurrence -- the
     round-5 sequence (4-row kernels, dgates of both layers as compact images only).  The backward kernel at 8 rows per group and two
     roles runs 2.55 us per step against 2 x 1.62, and the chunked dX GEMMs (N = 1024, K = 4096: 224 tiles of a chunk) cost 3 x the one
-    GEMM -- measured a loss of 0.25 ms per flow (profiles/r06_pair_pipeline.log); the forward pipeline stands on its own."""
+    GEMM -- measured a loss of 0.25 ms per flow (profiles/r06_pair_pipeline.log) for the pipeline with fp32 dgates rows and per-chunk image
+    passes; the pipeline over one dgates image (_pair_backward_pipeline_img) is faster than this form and is the default -- this one
+    serves FLOWTRON_LSTM_PAIR_BWD=0."""
     w_hh0, w_ih1, w_hh1, lens, y0, g0, c0, y1, g1, c1 = ctx.saved_tensors
     T, B, H = y1.shape
     H4, mode, rm = 4 * H, ctx.mode, ctx.rowmap
@@ -1537,6 +1579,53 @@ def _pair_backward_sequential(ctx, dy1, w_img, img_only):
 
 
 DecoderPairFn._backward_sequential = staticmethod(_pair_backward_sequential)
+
+
+def _pair_backward_pipeline_img(ctx, dy1, w_img, n, edges, rms):
+    """DecoderPairFn.backward as a pipeline over n time windows with the sequential form's data flow: BOTH layers' dgates leave their
+    recurrences as the whole-sequence batch-major 16-bit images alone (column sums = the bias gradients), and chunk c's dX GEMM reads its
+    rows out of layer 1's image through a row list (gemm_img a_rows; ChunkGather) -- no fp32 dgates, no per-chunk image pass, no second
+    image of the whole sequence.  A chunk's list holds rows of that chunk only, all written by the launch in front of the GEMM; the
+    separator rows and the zero tail of the images are written by the last launch (the windows with t0 == 0), and only the weight-gradient
+    GEMMs behind it read them.
+    Carried state: NOT zeroed.  The first window of a layer runs with carry_in = False and never reads it; every non-empty window writes the
+    state of every batch row before it ends (also of a group without steps), and the next window of that layer is a later launch on the
+    same stream -- what the forward pipeline relies on for its own state."""
+    w_hh0, w_ih1, w_hh1, lens, y0, g0, c0, y1, g1, c1 = ctx.saved_tensors
+    T, B, H = y1.shape
+    H4, mode, rm = 4 * H, ctx.mode, ctx.rowmap
+    dev = dy1.device
+    f = dict(device=dev, dtype=torch.float32)
+    gr = _chunk_gathers(rms, lens, edges)
+    d_img1, d_img0 = Bf16Image.empty_rows(H4, rm, mode, dev), Bf16Image.empty_rows(H4, rm, mode, dev)
+    dy0 = torch.empty(T, B, H, **f)
+    st = torch.empty(2, B * (H4 + H), **f)                   # per layer: da [B, 4 H] | dc [B, H]
+    sb1, sb0 = (st[0, :B * H4], st[0, B * H4:]), (st[1, :B * H4], st[1, B * H4:])
+    wb0, wb1 = roles_wimg(w_hh0, mode, True), roles_wimg(w_hh1, mode, True)
+    for j in range(n + 1):
+        c = n - 1 - j                                        # layer 1's chunk in this launch; layer 0 runs chunk c + 1
+        roles = []
+        if j < n:
+            roles.append(bwd_role(dy1, lens, g1, c1, None, wb1, edges[c], edges[c + 1], sb1, carry_in=c < n - 1, dimg=d_img1))
+        if j > 0:
+            roles.append(bwd_role(dy0, lens, g0, c0, None, wb0, edges[c + 1], edges[c + 2], sb0, carry_in=c + 1 < n - 1, dimg=d_img0))
+        roles_launch(roles, 8 if len(roles) == 2 else 4, mode, dev, backward=True)
+        if j < n:
+            # dy0 of chunk c = dgates1 W_ih1 over the chunk's valid rows, gathered from the whole-sequence image
+            a, b = edges[c], edges[c + 1]
+            gemm_img(d_img1, 0, d_img1.ptr(), w_img, 1, w_img.ptr(), dy0[a:b], gr[c].cap, H, H4, H, rowmap=gr[c], compact=1, a_rows=gr[c].a_rows)
+    y0_img, y1_img = y_image(y0, T * B, H, mode, rm), y_image(y1, T * B, H, mode, rm)
+    dW_hh1, dW_ih1, dW_hh0 = weight_grad_out(w_hh1), weight_grad_out(w_ih1), weight_grad_out(w_hh0)
+    gemm_img(d_img1, 1, d_img1.ptr(1), y1_img, 1, y1_img.ptr(0), dW_hh1, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=1)
+    gemm_img(d_img1, 1, d_img1.ptr(), y0_img, 1, y0_img.ptr(), dW_ih1, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2)
+    gemm_img(d_img0, 1, d_img0.ptr(1), y0_img, 1, y0_img.ptr(0), dW_hh0, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=1)
+    dgx0 = image_only_gradient((T, B, H4), dev, ctx.gx_dtype)
+    _handoff_put_image_only(dgx0, d_img0)
+    db1 = d_img1.colsum
+    return dgx0, dW_hh0, dW_ih1, db1, db1, dW_hh1, None, None, None, None, None
+
+
+DecoderPairFn._backward_pipeline_img = staticmethod(_pair_backward_pipeline_img)
 
 
 def decoder_pair(x, lens, p, mode, xs_extra, rowmap, fill, gate, nchunks):

@@ -67,6 +67,10 @@ extern "C" {
 #endif
 
 #define FT_ABI_VERSION 14
+/* (ft_gemm_img_args grew its trailing a_rows field and ft_chunk_gather_rows was added WITHOUT a new number: 14 therefore names two struct
+ * layouts, and a caller's ft_abi_version() check cannot tell a library built before the field from one built after it.  Callers zero-
+ * initialise the struct and are built together with the library (flowtron_amd/build.py rebuilds on any header change); a binding kept
+ * outside this tree must be rebuilt against this header.) */
 
 enum { FT_OK = 0, FT_EINVAL = -1, FT_EHIP = -2, FT_EUNSUPPORTED = -3 };
 enum { FT_F32 = 0, FT_BF16 = 1, FT_F16 = 2 };
@@ -140,6 +144,12 @@ typedef struct {
      * the fp32 atomics of FT_GEMM_SPLITK are not (their order varies from run to run).  For FORWARD GEMMs with few output tiles and
      * a long reduction (the encoder convolutions' split-image product, flowtron.py:499-502); NULL / 0: never splits. */
     void* split_work; size_t split_work_bytes;
+    /* optional row gather of A (device list, NULL = none): with compact = 1, a_kmajor = 0, no split-K flag and K % 64 == 0 (anything else:
+     * FT_EINVAL) compact row m < *rows_dev reads image row a_rows[m] of A instead of row m; the rows of the last tile at or beyond
+     * *rows_dev read row a_rows[*rows_dev - 1] (their outputs are dropped), so A need not hold zeros anywhere.  Same k order as the plain
+     * call: the result equals that of an image whose rows were gathered beforehand, bit for bit.  The decoder pair's backward pipeline
+     * reads the rows of ONE time chunk out of the batch-major dgates image this way (ft_chunk_gather_rows). */
+    const int32_t* a_rows;
 } ft_gemm_img_args;
 size_t ft_gemm_img_split_work_bytes(int M, int N, int K);
 size_t ft_bf16_image_bytes(int64_t rows, int64_t cols);
@@ -186,6 +196,12 @@ int ft_bf16_image_table_f16(const ft_img_desc* descs, int n, void* stream);
  * values), else -1 (a zero row).  rowmap needs T*B + B entries; rows_dev[0] = sum_b (lens[b] + 1).  The separator rows make the
  * one-step shift of the recurrent weight gradient (dW_hh = sum_t dgates_t^T h_{t-1}) a one-ROW shift in compact space. */
 int ft_rowmap_build(const int32_t* lens, int32_t* rowmap, int32_t* rows_dev, int T, int B, void* stream);
+/* The row lists of the time chunk [t0, t1) of that batch, for a GEMM over the chunk's rows that reads them out of the WHOLE sequence's
+ * compact image (ft_gemm_img_args.a_rows): the chunk's compact rows are ft_rowmap_build's over the lengths clamp(lens[b] - t0, 0, t1 - t0)
+ * (so *rows_dev is that map's).  Compact row i = (t, b), t local to the chunk: a_rows[i] = off_b + t0 + t with off_b = sum over b' < b of
+ * (lens[b'] + 1), rowmap[i] = t * B + b.  The chunk's separator rows are dropped (rowmap -1) and read a valid row of the chunk: the image's
+ * own separator rows need not have been written yet.  Both lists need (t1 - t0) * B + B entries. */
+int ft_chunk_gather_rows(const int32_t* lens, int32_t* a_rows, int32_t* rowmap, int T, int B, int t0, int t1, void* stream);
 /* compact image: image row i = bf16(src row rowmap[i]) for i < *rows_dev (negative: zeros), zeros up to
  * ceil256(*rows_dev + 32); dst holds ft_bf16_image_bytes(cap_rows, cols).  colsum (optional) as ft_bf16_image_colsum. */
 int ft_bf16_image_rows(const float* src, int64_t ld, int64_t cap_rows, int64_t cols, void* dst, float* colsum,

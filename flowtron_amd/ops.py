@@ -1329,14 +1329,16 @@ def roles_plan(B, backward):
     return out
 
 
-_PAIR_CHUNKS_BWD = int(_os.environ.get("FLOWTRON_LSTM_PAIR_BWD", "3"))   # chunks of the pair's BACKWARD pipeline; 0 = sequential, -1 = as forward
+_PAIR_CHUNKS_BWD = int(_os.environ.get("FLOWTRON_LSTM_PAIR_BWD", "3"))   # windows of the pair's BACKWARD pipeline (_pair_backward_pipeline); 0 = the sequential form, -1 = as forward
 _PAIR_CHUNKS = int(_os.environ.get("FLOWTRON_LSTM_PAIR", "6"))       # time chunks of the decoder layer pair pipeline; 0 = one recurrence per launch
 
 
 def decoder_pair_chunks(B, H, mode, device, T):
     """number of time chunks the two decoder layers are pipelined over (DecoderPairFn), or 0: the pair needs both recurrences on
-    R = 8 rows per XCD, four XCDs each (B <= 32), the persistent kernels' shape and a sequence long enough to chunk"""
-    if _PAIR_CHUNKS <= 0 or B > 32 or T < 4 * _PAIR_CHUNKS or not lstm_persist_groups(B, H, False, mode, device):
+    R = 8 rows per XCD, four XCDs each (B <= 32), the persistent kernels' shape (hence 16-bit operands), a sequence long enough to chunk
+    and the compact operand images its backward works on throughout (DecoderPairFn.forward states the same)"""
+    if (_PAIR_CHUNKS <= 0 or B > 32 or T < 4 * _PAIR_CHUNKS or not lstm_persist_groups(B, H, False, mode, device)
+            or not images_apply(mode, 4 * H, H, (T - 1) * B)):
         return 0
     return _PAIR_CHUNKS
 
@@ -1372,7 +1374,8 @@ def _chunk_rowmaps(lens, edges, B):
 
 def _gather_gemm_on():
     """ft_gemm_img's row gather lives in the 64-wide single-buffer kernel alone: under the library's A/B hooks that switch that kernel off
-    (FT_GEMM_BF16_WIDE=0, FT_GEMM_BF16_TILE=256; read per call there, so per call here) the pipeline keeps its fp32-rows form"""
+    (FT_GEMM_BF16_WIDE=0, FT_GEMM_BF16_TILE=256; read per call there, so per call here) the pair's backward takes the sequential form,
+    whose one dX GEMM gathers nothing"""
     def num(name, default):
         try:
             return int(_os.environ.get(name, default))
@@ -1410,9 +1413,14 @@ class DecoderPairFn(torch.autograd.Function):
     """Both decoder LSTM layers of a flow (nn.LSTM(.., num_layers=2), flowtron.py:654-655, 689-694) as ONE pipeline over n time chunks:
     launch k runs layer 0 on chunk k (XCDs 0-3, 8 batch rows each) and layer 1 on chunk k - 1 (XCDs 4-7) CONCURRENTLY
     (csrc/lstm_roles.hip: two roles per launch, carried state), and layer 1's input projection of chunk k -- a chip-filling GEMM
-    over the chunk's valid rows -- runs between launch k and launch k + 1.  Backward the other way round: layer 1 on chunk c, layer 0 on
-    chunk c + 1, the chunk's dX GEMM (dy0 = dgates1 W_ih1) in between.  The dependency chain of the pair is (1 + 1/n) T steps of the
-    8-row kernel instead of 2 T steps of the 4-row one; the arithmetic is that of two single launches (forward bit-identical)."""
+    over the chunk's valid rows -- runs between launch k and launch k + 1.  The dependency chain of the pair is (1 + 1/n) T steps of the
+    8-row kernel instead of 2 T steps of the 4-row one; the arithmetic is that of two single launches (forward bit-identical).
+    Backward has two forms, both over the compact 16-bit dgates images of the whole sequence: the same pipeline the other way round
+    (_pair_backward_pipeline, the default: layer 1 on window c, layer 0 on window c + 1, the window's dX GEMM dy0 = dgates1 W_ih1 in
+    between, over FLOWTRON_LSTM_PAIR_BWD windows of its own), or two single recurrences around one dX GEMM (_pair_backward_sequential).
+    FLOWTRON_LSTM_PERSIST_IMG decides only how layer 0's dgates LEAVE the node (_pair_backward_return).
+    The node takes what model.Flowtron gives it where decoder_pair_chunks says yes, and nothing else: a RowMap over its own [T, B],
+    16-bit operands, T > 1 and a shape whose weight-gradient GEMMs run from images -- ValueError otherwise, there is no other path."""
 
     @staticmethod
     def forward(ctx, gx0, w_hh0, w_ih1, b_ih1, b_hh1, w_hh1, lens, mode, rowmap, gx_private, nchunks):
@@ -1420,6 +1428,11 @@ class DecoderPairFn(torch.autograd.Function):
         L.require_cuda(gx0, w_hh0, w_ih1, w_hh1, lens)
         T, B, H4 = gx0.shape
         H = H4 // 4
+        if rowmap is None or rowmap.T != T or rowmap.B != B:
+            raise ValueError("DecoderPairFn needs a RowMap over its own [T, B] = [%d, %d] (ops.row_map)" % (T, B))
+        if not L.is16(mode) or T <= 1 or not images_apply(mode, H4, H, (T - 1) * B):
+            raise ValueError("DecoderPairFn needs 16-bit operands, T > 1 and weight-gradient GEMMs large enough for operand images "
+                             "(mode %s, T %d, B %d, H %d); ops.decoder_pair_chunks says where the pair applies" % (mode, T, B, H))
         dev = gx0.device
         f = dict(device=dev, dtype=torch.float32)
         y0, g0, c0 = torch.empty(T, B, H, **f), torch.empty(T, B, H4, **f), torch.empty(T, B, H, **f)
@@ -1452,94 +1465,71 @@ class DecoderPairFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy1):
-        w_hh0, w_ih1, w_hh1, lens, y0, g0, c0, y1, g1, c1 = ctx.saved_tensors
-        dy1 = _c(dy1)
-        T, B, H = y1.shape
-        H4, mode, rm, n = 4 * H, ctx.mode, ctx.rowmap, ctx.nchunks
-        dev = dy1.device
-        f = dict(device=dev, dtype=torch.float32)
-        edges, rms = ctx.chunk_maps
-        # layer 0's dgates leave as the compact 16-bit image alone where the only consumer is the input projection's backward
-        img_ok = rm is not None and _PERSIST_IMG != "0" and images_apply(mode, H4, H, (T - 1) * B) and (ctx.gx_private or _PERSIST_IMG == "both")
-        img_only = img_ok and _PERSIST_IMG != "both" and not torch.is_anomaly_enabled()
-        w_img = ctx.w_img if ctx.w_img is not None else Bf16Image.of_weight(w_ih1, mode)     # (released by a first backward: retain_graph)
+        saved = ctx.saved_tensors                      # w_hh0, w_ih1, w_hh1, lens, y0, g0, c0, y1, g1, c1
+        T = saved[7].shape[0]
+        w_img = ctx.w_img if ctx.w_img is not None else Bf16Image.of_weight(saved[1], ctx.mode)     # (released by a first backward: retain_graph)
         ctx.w_img = None
-        nb = min(_PAIR_CHUNKS_BWD, T) if _PAIR_CHUNKS_BWD >= 0 else n      # (at most T windows: none is empty, the edges rise strictly)
-        if nb == 0 and rm is not None and img_ok and ctx.needs_input_grad[1] and ctx.needs_input_grad[5]:
-            return DecoderPairFn._backward_sequential(ctx, dy1, w_img, img_only)      # (before the pipeline's buffers: four fills less per pass)
-        if nb != n and nb > 0:
-            n = nb
-            edges = _chunk_edges(T, n)
-            rms = _chunk_rowmaps(lens, edges, B)
-        assert all(a < b for a, b in zip(edges, edges[1:])), "empty time window in the pair's backward pipeline"
-        if rm is not None and img_only and ctx.needs_input_grad[1] and ctx.needs_input_grad[5] and T > 1 and _gather_gemm_on():
-            return DecoderPairFn._backward_pipeline_img(ctx, dy1, w_img, n, edges, rms)
-        dgx1 = torch.empty(T, B, H4, **f)
-        dy0 = torch.empty(T, B, H, **f)
-        d_img0 = Bf16Image.empty_rows(H4, rm, mode, dev) if img_ok else None
-        dgx0 = None if img_only else torch.empty(T, B, H4, **f)
-        sb1 = (torch.zeros(B, H4, **f), torch.zeros(B, H, **f))
-        sb0 = (torch.zeros(B, H4, **f), torch.zeros(B, H, **f))
-        wb0, wb1 = roles_wimg(w_hh0, mode, True), roles_wimg(w_hh1, mode, True)
-        for j in range(n + 1):
-            c = n - 1 - j                                        # layer 1's chunk in this launch; layer 0 runs chunk c + 1
-            roles = []
-            if j < n:
-                roles.append(bwd_role(dy1, lens, g1, c1, dgx1, wb1, edges[c], edges[c + 1], sb1, carry_in=c < n - 1))
-            if j > 0:
-                roles.append(bwd_role(dy0, lens, g0, c0, dgx0, wb0, edges[c + 1], edges[c + 2], sb0, carry_in=c + 1 < n - 1, dimg=d_img0))
-            roles_launch(roles, 8 if len(roles) == 2 else 4, mode, dev, backward=True)
-            if j < n:
-                # dy0 of chunk c = dgates1 W_ih1 over the chunk's valid rows
-                a, b = edges[c], edges[c + 1]
-                d_img = Bf16Image(dgx1[a:b].reshape((b - a) * B, H4), mode=mode, rowmap=rms[c])
-                gemm_img(d_img, 0, d_img.ptr(), w_img, 1, w_img.ptr(), dy0[a:b], rms[c].cap, H, H4, H, rowmap=rms[c], compact=1)
-        # weight / bias gradients over the whole sequence (compact rows; the one-step shift of dW_hh = one compact row)
-        dW_hh0 = dW_ih1 = dW_hh1 = db1 = None
-        need = ctx.needs_input_grad
-        compact_ok = rm is not None and T > 1 and images_apply(mode, H4, H, (T - 1) * B)
-        if need[1] or need[2] or need[3] or need[4] or need[5]:
-            if compact_ok:
-                d_img1 = Bf16Image(dgx1.reshape(T * B, H4), colsum=True, mode=mode, rowmap=rm)
-                db1 = d_img1.colsum
-                y0_img, y1_img = shared_image(y0, T * B, H, mode, rm), shared_image(y1, T * B, H, mode, rm)
-                if need[5]:
-                    dW_hh1 = weight_grad_out(w_hh1)
-                    gemm_img(d_img1, 1, d_img1.ptr(1), y1_img, 1, y1_img.ptr(0), dW_hh1, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=1)
-                if need[2]:
-                    dW_ih1 = weight_grad_out(w_ih1)
-                    gemm_img(d_img1, 1, d_img1.ptr(), y0_img, 1, y0_img.ptr(), dW_ih1, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2)
-                if need[1]:
-                    d0 = d_img0 if d_img0 is not None else Bf16Image(dgx0.reshape(T * B, H4), colsum=True, mode=mode, rowmap=rm)
-                    dW_hh0 = weight_grad_out(w_hh0)
-                    gemm_img(d0, 1, d0.ptr(1), y0_img, 1, y0_img.ptr(0), dW_hh0, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=1)
-                    d_img0 = d0
-            else:
-                rows = (T - 1) * B
-                db1 = colsum(dgx1, T * B, H4, H4)
-                dW_hh1, dW_ih1, dW_hh0 = torch.zeros_like(w_hh1), torch.zeros_like(w_ih1), torch.zeros_like(w_hh0)
-                if T > 1:
-                    gemm_raw(dgx1[1:], y1[:-1], dW_hh1, H4, H, rows, 1, H4, H, 1, H, mode=mode, splitk=True)
-                    gemm_raw(dgx0[1:], y0[:-1], dW_hh0, H4, H, rows, 1, H4, H, 1, H, mode=mode, splitk=True)
-                gemm_raw(dgx1, y0, dW_ih1, H4, H, T * B, 1, H4, H, 1, H, mode=mode, splitk=True)
-        if img_only:
-            dgx0 = image_only_gradient((T, B, H4), dev, ctx.gx_dtype)
-            _handoff_put_image_only(dgx0, d_img0)
-        elif d_img0 is not None:
-            if ctx.gx_dtype != torch.float32:
-                dgx0 = dgx0.to(ctx.gx_dtype)
-            _handoff_put(dgx0, d_img0)
-        return dgx0, dW_hh0, dW_ih1, db1, db1, dW_hh1, None, None, None, None, None
+        n = min(_PAIR_CHUNKS_BWD, T) if _PAIR_CHUNKS_BWD >= 0 else ctx.nchunks      # (at most T windows: none is empty, the edges rise strictly)
+        # whether dgx0 must carry real fp32 values: beside the image, which is the only form inside the node
+        keep_f32 = _PERSIST_IMG != "1" or torch.is_anomaly_enabled() or not ctx.gx_private
+        if n == 0 or not _gather_gemm_on():
+            return _pair_backward_sequential(ctx, saved, _c(dy1), w_img, keep_f32)
+        return _pair_backward_pipeline(ctx, saved, _c(dy1), w_img, n, keep_f32)
 
 
-def _pair_backward_sequential(ctx, dy1, w_img, img_only):
+def _leave_dgates(dgx, d_img, img_only, shape, gx_dtype):
+    """What a recurrence's backward returns for its gx.  img_only: the NaN face of the dgates image `d_img` (a foreign reader sees NaN,
+    never unwritten memory), the image handed to the input projection's backward as the ONLY form.  Else the fp32 rows `dgx` in gx's
+    dtype (16-bit gx rows, gx16_ok, in a pass that keeps fp32 dgates: autograd wants the gradient in gx's dtype, and the hand-off is
+    keyed on the tensor it will carry), with `d_img` -- where there is one -- handed over beside them: the projection's backward reads
+    the same dgates."""
+    if img_only:
+        dgx = image_only_gradient(shape, d_img.buf.device, gx_dtype)
+        _handoff_put_image_only(dgx, d_img)
+        return dgx
+    if dgx.dtype != gx_dtype:
+        dgx = dgx.to(gx_dtype)
+    if d_img is not None:
+        _handoff_put(dgx, d_img)
+    return dgx
+
+
+def _pair_weight_grads(ctx, saved, d_img1, d_img0):
+    """(dW_hh1, dW_ih1, dW_hh0) of the pair from the compact dgates images of the whole sequence (the one-step shift of a dW_hh = one
+    compact row); None where the weight needs no gradient"""
+    w_hh0, w_ih1, w_hh1, _, y0, _, _, y1 = saved[:8]
+    T, B, H = y1.shape
+    rm, need = ctx.rowmap, ctx.needs_input_grad
+    y0_img = y_image(y0, T * B, H, ctx.mode, rm) if need[1] or need[2] else None
+    y1_img = y_image(y1, T * B, H, ctx.mode, rm) if need[5] else None
+    jobs = [(need[5], w_hh1, d_img1, y1_img, 1), (need[2], w_ih1, d_img1, y0_img, 0), (need[1], w_hh0, d_img0, y0_img, 1)]
+    outs = [weight_grad_out(w) if on else None for on, w, _, _, _ in jobs]
+    for dW, (on, _, d, y, shift) in zip(outs, jobs):
+        if on:
+            gemm_img(d, 1, d.ptr(shift), y, 1, y.ptr(0), dW, 4 * H, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=shift)
+    return outs
+
+
+def _pair_backward_return(ctx, saved, d_img1, d_img0, dgx0):
+    """the tail both backward forms share: the weight gradients, and dgx0 as FLOWTRON_LSTM_PERSIST_IMG says it leaves the node -- the image
+    alone (dgx0 None: "1" with a private gx outside anomaly mode), fp32 rows with the image beside them (both, anomaly mode), or fp32
+    rows alone ("0", a gx that is not the projection's own)"""
+    dW_hh1, dW_ih1, dW_hh0 = _pair_weight_grads(ctx, saved, d_img1, d_img0)
+    T, B, H = saved[7].shape
+    hand = _PERSIST_IMG != "0" and (ctx.gx_private or _PERSIST_IMG == "both")
+    dgx0 = _leave_dgates(dgx0, d_img0 if hand else None, dgx0 is None, (T, B, 4 * H), ctx.gx_dtype)
+    db1 = d_img1.colsum
+    return dgx0, dW_hh0, dW_ih1, db1, db1, dW_hh1, None, None, None, None, None
+
+
+def _pair_backward_sequential(ctx, saved, dy1, w_img, keep_f32):
     """DecoderPairFn.backward without the pipeline: layer 1's recurrence, ONE dX GEMM over all valid rows, layer 0's recurrence -- the
-    round-5 sequence (4-row kernels, dgates of both layers as compact images only).  The backward kernel at 8 rows per group and two
-    roles runs 2.55 us per step against 2 x 1.62, and the chunked dX GEMMs (N = 1024, K = 4096: 224 tiles of a chunk) cost 3 x the one
-    GEMM -- measured a loss of 0.25 ms per flow (profiles/r06_pair_pipeline.log) for the pipeline with fp32 dgates rows and per-chunk image
-    passes; the pipeline over one dgates image (_pair_backward_pipeline_img) is faster than this form and is the default -- this one
-    serves FLOWTRON_LSTM_PAIR_BWD=0."""
-    w_hh0, w_ih1, w_hh1, lens, y0, g0, c0, y1, g1, c1 = ctx.saved_tensors
+    round-5 sequence (4-row kernels, dgates of both layers as compact images; keep_f32: layer 0's as fp32 rows beside its image).  The
+    backward kernel at 8 rows per group and two roles runs 2.55 us per step against 2 x 1.62, and the chunked dX GEMMs (N = 1024,
+    K = 4096: 224 tiles of a chunk) cost 3 x the one GEMM; the pipeline over one dgates image (_pair_backward_pipeline) is still faster
+    than this form and is the default -- this one serves FLOWTRON_LSTM_PAIR_BWD=0, and the library's A/B hooks that switch the
+    gathering GEMM kernel off (_gather_gemm_on)."""
+    w_hh0, w_ih1, w_hh1, lens, y0, g0, c0, y1, g1, c1 = saved
     T, B, H = y1.shape
     H4, mode, rm = 4 * H, ctx.mode, ctx.rowmap
     dev = dy1.device
@@ -1556,49 +1546,38 @@ def _pair_backward_sequential(ctx, dy1, w_img, img_only):
         return img
 
     d_img1 = recurrence(dy1, g1, c1, w_hh1)
-    y0_img, y1_img = y_image(y0, T * B, H, mode, rm), y_image(y1, T * B, H, mode, rm)
-    dW_hh1, dW_ih1, dW_hh0 = weight_grad_out(w_hh1), weight_grad_out(w_ih1), weight_grad_out(w_hh0)
-    gemm_img(d_img1, 1, d_img1.ptr(1), y1_img, 1, y1_img.ptr(0), dW_hh1, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=1)
     dy0 = torch.empty(T, B, H, device=dev, dtype=torch.float32)
     gemm_img(d_img1, 0, d_img1.ptr(), w_img, 1, w_img.ptr(), dy0, rm.cap, H, H4, H, rowmap=rm, compact=1)
-    gemm_img(d_img1, 1, d_img1.ptr(), y0_img, 1, y0_img.ptr(), dW_ih1, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2)
-    # layer 0's dgates: the image alone, or (anomaly mode, FLOWTRON_LSTM_PERSIST_IMG=both) fp32 rows beside it -- real values for a
-    # consumer that reads them, as LSTMSeqFn.backward
-    dgx0 = None if img_only else torch.empty(T, B, H4, device=dev, dtype=torch.float32)
+    dgx0 = torch.empty(T, B, H4, device=dev, dtype=torch.float32) if keep_f32 else None
     d_img0 = recurrence(dy0, g0, c0, w_hh0, dgx0)
-    gemm_img(d_img0, 1, d_img0.ptr(1), y0_img, 1, y0_img.ptr(0), dW_hh0, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=1)
-    if img_only:
-        dgx0 = image_only_gradient((T, B, H4), dev, ctx.gx_dtype)
-        _handoff_put_image_only(dgx0, d_img0)
-    else:
-        if ctx.gx_dtype != torch.float32:
-            dgx0 = dgx0.to(ctx.gx_dtype)
-        _handoff_put(dgx0, d_img0)
-    db1 = d_img1.colsum
-    return dgx0, dW_hh0, dW_ih1, db1, db1, dW_hh1, None, None, None, None, None
+    return _pair_backward_return(ctx, saved, d_img1, d_img0, dgx0)
 
 
-DecoderPairFn._backward_sequential = staticmethod(_pair_backward_sequential)
-
-
-def _pair_backward_pipeline_img(ctx, dy1, w_img, n, edges, rms):
+def _pair_backward_pipeline(ctx, saved, dy1, w_img, n, keep_f32):
     """DecoderPairFn.backward as a pipeline over n time windows with the sequential form's data flow: BOTH layers' dgates leave their
-    recurrences as the whole-sequence batch-major 16-bit images alone (column sums = the bias gradients), and chunk c's dX GEMM reads its
-    rows out of layer 1's image through a row list (gemm_img a_rows; ChunkGather) -- no fp32 dgates, no per-chunk image pass, no second
-    image of the whole sequence.  A chunk's list holds rows of that chunk only, all written by the launch in front of the GEMM; the
-    separator rows and the zero tail of the images are written by the last launch (the windows with t0 == 0), and only the weight-gradient
-    GEMMs behind it read them.
+    recurrences as the whole-sequence batch-major 16-bit images (column sums = the bias gradients; keep_f32: layer 0's as fp32 rows
+    beside its image, which the roles kernel writes when it gets both), and chunk c's dX GEMM reads its rows out of layer 1's image
+    through a row list (gemm_img a_rows; ChunkGather) -- no fp32 dgates of layer 1, no per-chunk image pass, no second image of the
+    whole sequence.  A chunk's list holds rows of that chunk only, all written by the launch in front of the GEMM; the separator rows and
+    the zero tail of the images are written by the last launch (the windows with t0 == 0), and only the weight-gradient GEMMs behind it
+    read them.
     Carried state: NOT zeroed.  The first window of a layer runs with carry_in = False and never reads it; every non-empty window writes the
     state of every batch row before it ends (also of a group without steps), and the next window of that layer is a later launch on the
     same stream -- what the forward pipeline relies on for its own state."""
-    w_hh0, w_ih1, w_hh1, lens, y0, g0, c0, y1, g1, c1 = ctx.saved_tensors
+    w_hh0, w_ih1, w_hh1, lens, y0, g0, c0, y1, g1, c1 = saved
     T, B, H = y1.shape
     H4, mode, rm = 4 * H, ctx.mode, ctx.rowmap
     dev = dy1.device
     f = dict(device=dev, dtype=torch.float32)
+    edges, rms = ctx.chunk_maps
+    if n != ctx.nchunks:
+        edges = _chunk_edges(T, n)
+        rms = _chunk_rowmaps(lens, edges, B)
+    assert all(a < b for a, b in zip(edges, edges[1:])), "empty time window in the pair's backward pipeline"
     gr = _chunk_gathers(rms, lens, edges)
     d_img1, d_img0 = Bf16Image.empty_rows(H4, rm, mode, dev), Bf16Image.empty_rows(H4, rm, mode, dev)
     dy0 = torch.empty(T, B, H, **f)
+    dgx0 = torch.empty(T, B, H4, **f) if keep_f32 else None
     st = torch.empty(2, B * (H4 + H), **f)                   # per layer: da [B, 4 H] | dc [B, H]
     sb1, sb0 = (st[0, :B * H4], st[0, B * H4:]), (st[1, :B * H4], st[1, B * H4:])
     wb0, wb1 = roles_wimg(w_hh0, mode, True), roles_wimg(w_hh1, mode, True)
@@ -1608,24 +1587,13 @@ def _pair_backward_pipeline_img(ctx, dy1, w_img, n, edges, rms):
         if j < n:
             roles.append(bwd_role(dy1, lens, g1, c1, None, wb1, edges[c], edges[c + 1], sb1, carry_in=c < n - 1, dimg=d_img1))
         if j > 0:
-            roles.append(bwd_role(dy0, lens, g0, c0, None, wb0, edges[c + 1], edges[c + 2], sb0, carry_in=c + 1 < n - 1, dimg=d_img0))
+            roles.append(bwd_role(dy0, lens, g0, c0, dgx0, wb0, edges[c + 1], edges[c + 2], sb0, carry_in=c + 1 < n - 1, dimg=d_img0))
         roles_launch(roles, 8 if len(roles) == 2 else 4, mode, dev, backward=True)
         if j < n:
             # dy0 of chunk c = dgates1 W_ih1 over the chunk's valid rows, gathered from the whole-sequence image
             a, b = edges[c], edges[c + 1]
             gemm_img(d_img1, 0, d_img1.ptr(), w_img, 1, w_img.ptr(), dy0[a:b], gr[c].cap, H, H4, H, rowmap=gr[c], compact=1, a_rows=gr[c].a_rows)
-    y0_img, y1_img = y_image(y0, T * B, H, mode, rm), y_image(y1, T * B, H, mode, rm)
-    dW_hh1, dW_ih1, dW_hh0 = weight_grad_out(w_hh1), weight_grad_out(w_ih1), weight_grad_out(w_hh0)
-    gemm_img(d_img1, 1, d_img1.ptr(1), y1_img, 1, y1_img.ptr(0), dW_hh1, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=1)
-    gemm_img(d_img1, 1, d_img1.ptr(), y0_img, 1, y0_img.ptr(), dW_ih1, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2)
-    gemm_img(d_img0, 1, d_img0.ptr(1), y0_img, 1, y0_img.ptr(0), dW_hh0, H4, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=1)
-    dgx0 = image_only_gradient((T, B, H4), dev, ctx.gx_dtype)
-    _handoff_put_image_only(dgx0, d_img0)
-    db1 = d_img1.colsum
-    return dgx0, dW_hh0, dW_ih1, db1, db1, dW_hh1, None, None, None, None, None
-
-
-DecoderPairFn._backward_pipeline_img = staticmethod(_pair_backward_pipeline_img)
+    return _pair_backward_return(ctx, saved, d_img1, d_img0, dgx0)
 
 
 def decoder_pair(x, lens, p, mode, xs_extra, rowmap, fill, gate, nchunks):
@@ -1688,7 +1656,7 @@ class LSTMSeqFn(torch.autograd.Function):
         dgx = None                                   # allocated below unless the gradient leaves as an image only
         ng = lstm_persist_groups(B, H, ctx.reverse, ctx.mode, dy.device)
         wide = (not ng) and lstm_persist_slices(B, H, ctx.reverse, ctx.mode, dy.device)
-        d_img_k, img_only = None, False
+        d_img, img_only = None, False
         if wide:
             # slices of 64 rows at 8 per XCD group (2.5 us per step against 2 x 1.65 for two 32-row launches; 16 rows per group lose in the
             # backward kernel: 7.2 us per step for 128 rows, profiles/r06_persist_rows_per_group.log)
@@ -1708,14 +1676,14 @@ class LSTMSeqFn(torch.autograd.Function):
                 # the output waves leave the compact 16-bit image of dgates and its column sums INSTEAD of the fp32 rows (beside
                 # them with FLOWTRON_LSTM_PERSIST_IMG=both: 3.07 vs 2.91 us per step): no 450 MB dgx, no conversion pass over it.
                 # Anomaly mode inspects every gradient a node returns: it gets real values (both), not the NaN face of an image.
-                d_img_k = Bf16Image.empty_rows(4 * H, rm, ctx.mode, dy.device)
+                d_img = Bf16Image.empty_rows(4 * H, rm, ctx.mode, dy.device)
                 img_only = _PERSIST_IMG != "both" and not torch.is_anomaly_enabled()
                 if not img_only:
                     dgx = torch.empty(T, B, 4 * H, device=dy.device, dtype=torch.float32)
                 L.check(L.op16("ft_lstm_persist_bwd_img", ctx.mode)(L.ptr(dy), H, L.ptr(w_hh), L.ptr(lens), L.ptr(gates), L.ptr(cell),
                                                     None if img_only else L.ptr(dgx),
-                                                    L.ptr(work), L.ptr(st.status), T, B, H, ng, L.ptr(d_img_k.buf), d_img_k.ld,
-                                                    d_img_k.buf.numel() // (2 * d_img_k.ld), L.ptr(d_img_k.colsum), L.stream()),
+                                                    L.ptr(work), L.ptr(st.status), T, B, H, ng, L.ptr(d_img.buf), d_img.ld,
+                                                    d_img.buf.numel() // (2 * d_img.ld), L.ptr(d_img.colsum), L.stream()),
                         "ft_lstm_persist_bwd_img")
             else:
                 dgx = torch.empty(T, B, 4 * H, device=dy.device, dtype=torch.float32)
@@ -1727,14 +1695,6 @@ class LSTMSeqFn(torch.autograd.Function):
             work = torch.empty(L.lib().ft_lstm_workspace_bytes(B, H), device=dy.device, dtype=torch.uint8)
             L.check(L.lib().ft_lstm_seq_bwd(L.ptr(dy), H, L.ptr(w_hh), L.ptr(lens), L.ptr(gates), L.ptr(cell), L.ptr(dgx),
                                             L.ptr(work), T, B, H, int(ctx.reverse), ctx.mode, L.stream()), "ft_lstm_seq_bwd")
-        if img_only:
-            # the gradient autograd carries is the NaN face of the image: a foreign reader sees NaN, never unwritten memory
-            dgx = image_only_gradient((T, B, 4 * H), dy.device, ctx.gx_dtype)
-        dgx_f32 = dgx
-        if not img_only and ctx.gx_dtype != torch.float32:
-            # 16-bit gx rows (gx16_ok) in a pass that keeps fp32 dgates (anomaly mode, FLOWTRON_LSTM_PERSIST_IMG=both): autograd wants
-            # the gradient in gx's dtype -- cast here, so that the image hand-off below is keyed on the tensor it will carry
-            dgx = dgx.to(ctx.gx_dtype)
         dW = None
         if ctx.needs_input_grad[1]:
             # dW_hh[r,j] = sum_{t,b} da_t[b,r] * h_prev(t)[b,j];  h_prev = y[t-1] (fwd) / y[t+1] (reverse)
@@ -1744,24 +1704,20 @@ class LSTMSeqFn(torch.autograd.Function):
             if T > 1 and images_apply(ctx.mode, 4 * H, H, rows) and rm is not None:
                 # compact images (valid frames only, batch-major with one zero separator row per utterance): the one-step shift
                 # dgates_t <-> h_{t-1} is a shift by ONE compact row, and the utterance boundaries multiply with a separator
-                d_img = d_img_k if d_img_k is not None else Bf16Image(dgx_f32.reshape(T * B, 4 * H), colsum=True, mode=ctx.mode, rowmap=rm)
+                if d_img is None:
+                    d_img = Bf16Image(dgx.reshape(T * B, 4 * H), colsum=True, mode=ctx.mode, rowmap=rm)
                 y_img = y_image(y, T * B, H, ctx.mode, rm)
                 gemm_img(d_img, 1, d_img.ptr(1), y_img, 1, y_img.ptr(0), dW, 4 * H, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=1)
-                if img_only:
-                    _handoff_put_image_only(dgx, d_img)     # ... and ONLY the image exists
-                else:
-                    _handoff_put(dgx, d_img)    # the input projection's backward reads the same dgates
             elif T > 1 and images_apply(ctx.mode, 4 * H, H, rows):
                 # images of dgates / outputs over all T*B rows; the one-step shift is a row offset into them
-                d_img, y_img = Bf16Image(dgx_f32.reshape(T * B, 4 * H), colsum=True, mode=ctx.mode), shared_image(y, T * B, H, ctx.mode)
+                d_img, y_img = Bf16Image(dgx.reshape(T * B, 4 * H), colsum=True, mode=ctx.mode), shared_image(y, T * B, H, ctx.mode)
                 fwd = not ctx.reverse
                 gemm_img(d_img, 1, d_img.ptr(B if fwd else 0), y_img, 1, y_img.ptr(0 if fwd else B), dW, 4 * H, H, rows, H, beta=1.0, splitk=True)
-                _handoff_put(dgx, d_img)        # the input projection's backward reads the same dgates
             elif T > 1:
-                da = dgx_f32[1:] if not ctx.reverse else dgx_f32[:-1]
+                da = dgx[1:] if not ctx.reverse else dgx[:-1]
                 hp = y[:-1] if not ctx.reverse else y[1:]
                 gemm_raw(da, hp, dW, 4 * H, H, rows, 1, 4 * H, H, 1, H, mode=ctx.mode, splitk=True)
-        return dgx, dW, None, None, None, None, None
+        return _leave_dgates(dgx, d_img, img_only, (T, B, 4 * H), ctx.gx_dtype), dW, None, None, None, None, None
 
 
 MAX_STEP_BATCH = 64          # batch rows the launch-per-step recurrences and the bidirectional pair chain take (csrc/lstm.hip)

@@ -1503,17 +1503,30 @@ def _grads(p, x):
     return out
 
 
-def test_decoder_pair_sequential_backward_serves_anomaly_mode_and_both(env, monkeypatch):
-    """DecoderPairFn's sequential backward (FLOWTRON_LSTM_PAIR_BWD=0, the default): image-only mode hands layer 0's dgates to the input
-    projection as the image alone -- a foreign pre-hook sees NaN --, while anomaly mode (check_nan) and FLOWTRON_LSTM_PERSIST_IMG=both get
-    real fp32 values, and all three give the same gradients (bit for bit but the bias sums, whose column sums are fp32 atomics)"""
+def _same_grads(got, want, what):
+    """bit for bit but the bias sums, whose column sums are fp32 atomics"""
+    assert set(got) == set(want), what
+    for n in want:
+        assert torch.isfinite(got[n]).all(), (what, n)
+        if "bias" in n:
+            assert rel(got[n], want[n]) <= 1e-6, (what, n, rel(got[n], want[n]))
+        else:
+            assert torch.equal(got[n], want[n]), (what, n, rel(got[n], want[n]))
+
+
+@pytest.mark.parametrize("nch_bwd", [0, 3])
+def test_decoder_pair_sequential_backward_serves_anomaly_mode_and_both(env, monkeypatch, nch_bwd):
+    """DecoderPairFn's backward, sequential (FLOWTRON_LSTM_PAIR_BWD=0) and as the pipeline over 3 windows (the default): image-only mode
+    hands layer 0's dgates to the input projection as the image alone -- a foreign pre-hook sees NaN --, while anomaly mode (check_nan),
+    FLOWTRON_LSTM_PERSIST_IMG=both and =0 (no image leaves the node) get real fp32 values, and all four give the same gradients (bit for
+    bit but the bias sums, whose column sums are fp32 atomics)"""
     L, ops = env
     import contextlib
     T, B = 48, 32
     if not ops.lstm_persist_groups(B, 1024, False, L.FT_BF16, torch.device("cuda", torch.cuda.current_device())):
         pytest.skip("persistent recurrences not usable on this device")
     p, lens, x0, dh = _pair_setup(T, B)
-    monkeypatch.setattr(ops, "_PAIR_CHUNKS_BWD", 0)
+    monkeypatch.setattr(ops, "_PAIR_CHUNKS_BWD", nch_bwd)
     monkeypatch.setattr(ops, "_GX16", False)                          # (gx as fp32 rows in every mode: bitwise comparison)
 
     def run(img_mode, anomaly=False):
@@ -1544,6 +1557,92 @@ def test_decoder_pair_sequential_backward_serves_anomaly_mode_and_both(env, monk
                 assert rel(other[n], g_img[n]) <= 1e-6, n
             else:
                 assert torch.equal(other[n], g_img[n]), n
+    g_zero, seen = run("0")
+    assert bool(torch.isfinite(seen).all()), "FLOWTRON_LSTM_PERSIST_IMG=0: dgx0 leaves the pair as fp32 rows"
+    _same_grads(g_zero, g_both, "FLOWTRON_LSTM_PERSIST_IMG=0 against both")
+
+
+@pytest.mark.parametrize("nch_bwd", [3, 0])
+@pytest.mark.parametrize("frozen", ["weight_hh_l0", "weight_hh_l1"])
+def test_decoder_pair_backward_with_a_frozen_recurrent_weight(env, monkeypatch, frozen, nch_bwd):
+    """a recurrent weight of the pair that needs no gradient: its .grad stays None (its weight-gradient GEMM is skipped) and every other
+    gradient equals the unfrozen run of the same backward form -- pipeline over 3 windows and sequential"""
+    L, ops = env
+    T, B = 29, 5
+    if not ops.lstm_persist_groups(B, 1024, False, L.FT_BF16, torch.device("cuda", torch.cuda.current_device())):
+        pytest.skip("persistent recurrences not usable on this device")
+    p, lens, x0, dh = _pair_setup(T, B, seed=5)
+    monkeypatch.setattr(ops, "_PAIR_CHUNKS_BWD", nch_bwd)
+
+    def run():
+        x = x0.clone().requires_grad_(True)
+        h, _ = ops.decoder_pair(x, lens, p, L.FT_BF16, [], ops.row_map(lens, T, B), "dx", None, 4)
+        h.backward(dh)
+        torch.cuda.synchronize()
+        ops.check_persist_status()
+        assert (getattr(p, frozen).grad is None) == (not getattr(p, frozen).requires_grad)
+        out = {n: q.grad.clone() for n, q in p.named_parameters() if q.grad is not None}
+        out["x"] = x.grad.clone()
+        for q in p.parameters():
+            q.grad = None
+        return out
+
+    want = run()
+    getattr(p, frozen).requires_grad_(False)
+    got = run()
+    assert frozen in want and frozen not in got
+    del want[frozen]
+    _same_grads(got, want, "%s frozen, %d windows" % (frozen, nch_bwd))
+
+
+def test_decoder_pair_without_the_gathering_gemm_takes_the_sequential_form(env, monkeypatch):
+    """FT_GEMM_BF16_WIDE=0 (the library's A/B hook, read per call) switches off the GEMM kernel that gathers rows: with 3 windows asked for,
+    the pair's backward is the sequential form -- its gradients bit for bit (biases 1e-6)"""
+    L, ops = env
+    T, B = 29, 5
+    if not ops.lstm_persist_groups(B, 1024, False, L.FT_BF16, torch.device("cuda", torch.cuda.current_device())):
+        pytest.skip("persistent recurrences not usable on this device")
+    p, lens, x0, dh = _pair_setup(T, B, seed=6)
+
+    def run(nch_bwd):
+        monkeypatch.setattr(ops, "_PAIR_CHUNKS_BWD", nch_bwd)
+        x = x0.clone().requires_grad_(True)
+        h, _ = ops.decoder_pair(x, lens, p, L.FT_BF16, [], ops.row_map(lens, T, B), "dx", None, 4)
+        h.backward(dh)
+        torch.cuda.synchronize()
+        ops.check_persist_status()
+        return _grads(p, x)
+
+    monkeypatch.setenv("FT_GEMM_BF16_WIDE", "0")
+    want = run(0)
+    pipelines = []
+    real = ops._pair_backward_pipeline
+    monkeypatch.setattr(ops, "_pair_backward_pipeline", lambda *a: (pipelines.append(1), real(*a))[1])
+    got = run(3)
+    assert not pipelines, "the pipeline needs the gathering GEMM kernel"
+    _same_grads(got, want, "FT_GEMM_BF16_WIDE=0, 3 windows against sequential")
+
+
+def test_decoder_pair_states_its_preconditions(env, monkeypatch):
+    """DecoderPairFn.apply without a RowMap, and in fp32 mode: ValueError from forward, before anything is launched"""
+    L, ops = env
+    T, B, H = 29, 5, 1024
+    gx0 = torch.randn(T, B, 4 * H, device="cuda", requires_grad=True)
+    ws = [(torch.randn(4 * H, H, device="cuda") / 32).requires_grad_(True) for _ in range(3)]
+    bs = [torch.zeros(4 * H, device="cuda", requires_grad=True) for _ in range(2)]
+    lens = torch.tensor([T, 3, 11, 29, 1], dtype=torch.int32, device="cuda")
+    rm, rm_other = ops.row_map(lens, T, B), ops.row_map(lens[:4].contiguous(), T, 4)
+    torch.cuda.synchronize()
+    launched = []
+    for name in ("roles_launch", "roles_wimg", "gemm_img", "bias_sum"):
+        monkeypatch.setattr(ops, name, lambda *a, name=name, **kw: launched.append(name))
+    before = ops.PERSIST_LAUNCHES
+    for mode, rowmap in ((L.FT_BF16, None), (L.FT_BF16, rm_other), (L.FT_F32, rm)):
+        with pytest.raises(ValueError, match="DecoderPairFn needs"):
+            ops.DecoderPairFn.apply(gx0, ws[0], ws[1], bs[0], bs[1], ws[2], lens, mode, rowmap, True, 4)
+    assert not launched and ops.PERSIST_LAUNCHES == before
+    torch.cuda.synchronize()
+    ops.check_persist_status()
 
 
 @pytest.mark.parametrize("nch_bwd", [0, -1])

@@ -1,6 +1,6 @@
 """The decoder pair's backward pipeline over the whole-sequence dgates image: ft_gemm_img's row gather of the A operand (a_rows) against
-the same GEMM over an image whose rows were gathered beforehand, and DecoderPairFn's image-only pipeline branch against the fp32-rows
-pipeline it replaces (FLOWTRON_LSTM_PERSIST_IMG=both)."""
+the same GEMM over an image whose rows were gathered beforehand, and DecoderPairFn's backward pipeline against the fp32-rows pipeline
+it replaced, which lives on here as the yardstick (fp32_rows_pipeline)."""
 import types
 
 import pytest
@@ -169,13 +169,58 @@ def _pipe_setup(B):
     return (_PIPE_MODEL["p"], (torch.randn(T_PIPE, B, 128, generator=gen) * 0.3).cuda(), (torch.randn(T_PIPE, B, 1024, generator=gen) * 0.1).cuda())
 
 
+def fp32_rows_pipeline(L, ops, saved, dy1, rm, n, mode):
+    """The pair's backward as the library ran it before the pipeline over one dgates image, from the public primitives -- the yardstick:
+    layer 1's dgates as fp32 rows (dgx1), one image pass per chunk over the chunk's own RowMap in front of its dX GEMM, zeroed carried
+    state, layer 0's dgates as fp32 rows beside its whole-sequence image, and a second whole-sequence image (of dgx1, with the column
+    sums) for the weight gradients.  `saved`: the tensors DecoderPairFn.forward saved."""
+    w_hh0, w_ih1, w_hh1, lens, y0, g0, c0, y1, g1, c1 = saved
+    T, B, H = y1.shape
+    H4, dev = 4 * H, dy1.device
+    f = dict(device=dev, dtype=torch.float32)
+    edges = _edges(T, n)
+    rms = [ops.RowMap((lens - a).clamp(0, b - a).to(torch.int32), b - a, B) for a, b in zip(edges, edges[1:])]
+    w_img = ops.Bf16Image(w_ih1, mode=mode)
+    dgx1, dgx0, dy0 = torch.empty(T, B, H4, **f), torch.empty(T, B, H4, **f), torch.empty(T, B, H, **f)
+    d_img0 = ops.Bf16Image.empty_rows(H4, rm, mode, dev)
+    sb1 = (torch.zeros(B, H4, **f), torch.zeros(B, H, **f))
+    sb0 = (torch.zeros(B, H4, **f), torch.zeros(B, H, **f))
+    wb0, wb1 = ops.roles_wimg(w_hh0, mode, True), ops.roles_wimg(w_hh1, mode, True)
+    for j in range(n + 1):
+        c = n - 1 - j                                        # layer 1's chunk in this launch; layer 0 runs chunk c + 1
+        roles = []
+        if j < n:
+            roles.append(ops.bwd_role(dy1, lens, g1, c1, dgx1, wb1, edges[c], edges[c + 1], sb1, carry_in=c < n - 1))
+        if j > 0:
+            roles.append(ops.bwd_role(dy0, lens, g0, c0, dgx0, wb0, edges[c + 1], edges[c + 2], sb0, carry_in=c + 1 < n - 1, dimg=d_img0))
+        ops.roles_launch(roles, 8 if len(roles) == 2 else 4, mode, dev, backward=True)
+        if j < n:
+            a, b = edges[c], edges[c + 1]
+            d_img = ops.Bf16Image(dgx1[a:b].reshape((b - a) * B, H4), mode=mode, rowmap=rms[c])
+            ops.gemm_img(d_img, 0, d_img.ptr(), w_img, 1, w_img.ptr(), dy0[a:b], rms[c].cap, H, H4, H, rowmap=rms[c], compact=1)
+    d_img1 = ops.Bf16Image(dgx1.reshape(T * B, H4), colsum=True, mode=mode, rowmap=rm)
+    y0_img, y1_img = ops.Bf16Image(y0.reshape(T * B, H), mode=mode, rowmap=rm), ops.Bf16Image(y1.reshape(T * B, H), mode=mode, rowmap=rm)
+    dW_hh1, dW_ih1, dW_hh0 = torch.zeros_like(w_hh1), torch.zeros_like(w_ih1), torch.zeros_like(w_hh0)
+    kw = dict(beta=1.0, splitk=True, rowmap=rm, compact=2)
+    ops.gemm_img(d_img1, 1, d_img1.ptr(1), y1_img, 1, y1_img.ptr(0), dW_hh1, H4, H, rm.cap, H, k_shift=1, **kw)
+    ops.gemm_img(d_img1, 1, d_img1.ptr(), y0_img, 1, y0_img.ptr(), dW_ih1, H4, H, rm.cap, H, **kw)
+    ops.gemm_img(d_img0, 1, d_img0.ptr(1), y0_img, 1, y0_img.ptr(0), dW_hh0, H4, H, rm.cap, H, k_shift=1, **kw)
+    torch.cuda.synchronize()
+    ops.check_persist_status()
+    assert torch.isfinite(dgx0).all()
+    return {"weight_hh_l0": dW_hh0, "weight_ih_l1": dW_ih1, "weight_hh_l1": dW_hh1, "bias_ih_l1": d_img1.colsum, "bias_hh_l1": d_img1.colsum,
+            "dgx0 image": d_img0}
+
+
 @pytest.mark.parametrize("nch_bwd", [2, 3, -1])
 @pytest.mark.parametrize("B", [32, 5])
 def test_image_pipeline_equals_the_fp32_rows_pipeline(env, monkeypatch, B, nch_bwd):
-    """DecoderPairFn.backward over `nch_bwd` windows: the branch that keeps both layers' dgates as whole-sequence images and gathers each
-    chunk's dX rows out of layer 1's (default image mode) against the fp32-rows pipeline (FLOWTRON_LSTM_PERSIST_IMG=both).  dgx0 -- its
-    image, and the input projection's gradients made from it --, dW_hh0, dW_ih1 and dW_hh1 bit for bit; the bias gradient (fp32 atomics)
-    to 1e-6.  The allocator is filled with NaN before each run: a read of an image row (or of a carried state) nobody wrote would show."""
+    """DecoderPairFn.backward over `nch_bwd` windows -- both layers' dgates as whole-sequence images, each chunk's dX rows gathered out of
+    layer 1's -- against the fp32-rows pipeline it replaced (fp32_rows_pipeline above, on the tensors the node's forward saved): dgx0's
+    image, dW_hh0, dW_ih1 and dW_hh1 bit for bit; the bias gradient (fp32 atomics) to 1e-6.  And the node in image mode against itself
+    with FLOWTRON_LSTM_PERSIST_IMG=both (the same pipeline, fp32 rows of dgx0 beside the image): those and the input projection's
+    gradients made from dgx0 on the same terms.  The allocator is filled with NaN before each run: a read of an image row (or of a
+    carried state) nobody wrote would show."""
     L, ops = env
     T = T_PIPE
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -186,12 +231,17 @@ def test_image_pipeline_equals_the_fp32_rows_pipeline(env, monkeypatch, B, nch_b
     monkeypatch.setattr(ops, "_PAIR_CHUNKS_BWD", nch_bwd)
     monkeypatch.setattr(ops, "_GX16", False)                          # (gx as fp32 rows in both modes: bitwise comparison)
     taken = []
-    real_branch = ops.DecoderPairFn._backward_pipeline_img
-    monkeypatch.setattr(ops.DecoderPairFn, "_backward_pipeline_img", staticmethod(lambda *a: (taken.append(1), real_branch(*a))[1]))
+    real_branch = ops._pair_backward_pipeline
+    monkeypatch.setattr(ops, "_pair_backward_pipeline", lambda *a: (taken.append(a[4]), real_branch(*a))[1])
     imgs = []
     for name in ("_handoff_put", "_handoff_put_image_only"):
         real = getattr(ops, name)
         monkeypatch.setattr(ops, name, lambda t, img, *a, real=real, **kw: (imgs.append(img), real(t, img, *a, **kw))[1])
+    R = int(lens.sum().item()) + B
+
+    def image_rows(img):
+        Rz = min((R + 32 + 255) // 256 * 256, _img_rows16(img).shape[0])
+        return _img_rows16(img)[:Rz, :4096].clone()
 
     def run(img_mode):
         monkeypatch.setattr(ops, "_PERSIST_IMG", img_mode)
@@ -200,6 +250,7 @@ def test_image_pipeline_equals_the_fp32_rows_pipeline(env, monkeypatch, B, nch_b
         x = x0.clone().requires_grad_(True)
         rm = ops.row_map(lens, T, B)
         h, _ = ops.decoder_pair(x, lens, p, L.FT_BF16, [], rm, "dx", None, FWD_CHUNKS)
+        saved = h.grad_fn.saved_tensors
         h.backward(dh)
         torch.cuda.synchronize()
         ops.check_persist_status()
@@ -209,19 +260,20 @@ def test_image_pipeline_equals_the_fp32_rows_pipeline(env, monkeypatch, B, nch_b
             q.grad = None
         d_img0 = list({id(i): i for i in imgs if i.cols == 4096 and i.rowmap is rm}.values())     # (one hand-off helper calls the other)
         assert len(d_img0) == 1
-        R = int(lens.sum().item()) + B
-        Rz = min((R + 32 + 255) // 256 * 256, _img_rows16(d_img0[0]).shape[0])
-        out["dgx0 image"] = _img_rows16(d_img0[0])[:Rz, :4096].clone()
-        return out
+        out["dgx0 image"] = image_rows(d_img0[0])
+        return out, saved, rm
 
-    old = run("both")
-    assert not taken, "FLOWTRON_LSTM_PERSIST_IMG=both keeps the fp32-rows pipeline"
-    new = run("1")
-    assert len(taken) == 1, "the image pipeline branch did not run"
+    both, _, _ = run("both")
+    new, saved, rm = run("1")
+    assert taken == [n, n], "the image pipeline runs in both modes, over %d windows: %s" % (n, taken)
     assert bool((new["dgx0 image"][: int(lens[0])] != 0).any())
-    for k in old:
-        assert torch.isfinite(old[k].float()).all() and torch.isfinite(new[k].float()).all(), k
-        if "bias" in k:
-            assert rel(new[k], old[k]) <= 1e-6, (k, rel(new[k], old[k]))
-        else:
-            assert torch.equal(new[k], old[k]), (k, rel(new[k], old[k]))
+    torch.empty(64 << 20, device="cuda").fill_(float("nan"))
+    old = fp32_rows_pipeline(L, ops, saved, dh, rm, n, L.FT_BF16)
+    old["dgx0 image"] = image_rows(old["dgx0 image"])
+    for ref in (old, both):
+        for k in ref:
+            assert torch.isfinite(ref[k].float()).all() and torch.isfinite(new[k].float()).all(), k
+            if "bias" in k:
+                assert rel(new[k], ref[k]) <= 1e-6, (k, rel(new[k], ref[k]))
+            else:
+                assert torch.equal(new[k], ref[k]), (k, rel(new[k], ref[k]))

@@ -41,6 +41,10 @@ class GemmImgArgs(C.Structure):
                 ("split_work", _p), ("split_work_bytes", _sz), ("a_rows", _p)]
 
 
+class GemmImgPlan(C.Structure):
+    _fields_ = [(n, _i) for n in ("tile_rows", "stage_k", "gather", "atomics", "det", "splits", "chunk_w")]
+
+
 class LstmFwdRole(C.Structure):
     _fields_ = [("gx", _p), ("lens", _p), ("y", _p), ("ldy", _l), ("gates", _p), ("cell", _p), ("wimg", _p), ("state_h", _p), ("state_c", _p),
                 ("B", C.c_int32), ("ldb", C.c_int32), ("t0", C.c_int32), ("t1", C.c_int32), ("gx16", C.c_int32)]
@@ -95,6 +99,7 @@ SIGNATURES = {
     "ft_bf16_image_colsum_acc": ([_p, _l, _l, _l, _p, _p, _p], _i),
     "ft_gemm_img": ([C.POINTER(GemmImgArgs), _p], _i),
     "ft_gemm_img_split_work_bytes": ([_i, _i, _i], _sz),
+    "ft_gemm_img_plan": ([C.POINTER(GemmImgArgs), C.POINTER(GemmImgPlan)], _i),
     "ft_bf16_image_split3": ([_p, _l, _l, _l, _p, _i, _p], _i),
     "ft_bf16_image_split3_im2col": ([_p, _p, _i, _i, _i, _i, _p, _p], _i),
     "ft_bf16_image_split3_im2col_f16": ([_p, _p, _i, _i, _i, _i, _p, _p], _i),
@@ -222,7 +227,7 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = argt
             fn.restype = rest
-        if l.ft_abi_version() != 14:
+        if l.ft_abi_version() != 15:
             raise RuntimeError("libflowtron_hip.so ABI version mismatch")
         _lib = l
     return _lib

@@ -659,19 +659,22 @@ __global__ __launch_bounds__(256, SB ? 4 : (RTA == 256 || KS == 64) ? 2 : 4) voi
 // same in-order vmcnt the DMAs are waited on.  The single-buffer 128 x 128 x 64 form above -- four workgroups per CU, whole-line
 // pieces -- is faster on the same shapes (759 / 798 with 16-bit C) and everywhere else, so the tile was removed.)
 
+// The instantiation of gemm_bf16_k a call runs: chosen by plan_images, launched by launch_s, reported by ft_gemm_img_plan -- one value, so
+// the query cannot drift from the launch.  stage_k = 64: the single-buffer form; gather: its row-gathering variant.
+struct KernelSel { int tile_rows, stage_k, gather, atomics; };
+
 template <bool AKM, bool BKM>
-void launch_s(const BfP& p, dim3 grid, bool big, bool wide, hipStream_t st) {
-    const bool atomics = p.splits > 1 && p.c_slice == 0;       // (deterministic split-K runs the store epilogue, one C slice per k-slice)
-    if (big) {
-        if (atomics) hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, true, 256>), grid, dim3(256), 0, st, p);
+void launch_s(const BfP& p, dim3 grid, const KernelSel& k, hipStream_t st) {
+    if (k.tile_rows == 256) {
+        if (k.atomics) hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, true, 256>), grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, false, 256>), grid, dim3(256), 0, st, p);
     } else {
-        if (atomics) hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, true, 128>), grid, dim3(256), 0, st, p);
+        if (k.atomics) hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, true, 128>), grid, dim3(256), 0, st, p);
         else if constexpr (!(AKM && BKM)) {
             if constexpr (!AKM) {
-                if (wide && p.a_rows) { hipLaunchKernelGGL((gemm_bf16_k<false, BKM, false, 128, 64, true, true>), grid, dim3(256), 0, st, p); return; }
+                if (k.gather) { hipLaunchKernelGGL((gemm_bf16_k<false, BKM, false, 128, 64, true, true>), grid, dim3(256), 0, st, p); return; }
             }
-            if (wide) hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, false, 128, 64, true>), grid, dim3(256), 0, st, p);
+            if (k.stage_k == 64) hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, false, 128, 64, true>), grid, dim3(256), 0, st, p);
             else hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, false, 128>), grid, dim3(256), 0, st, p);
         } else hipLaunchKernelGGL((gemm_bf16_k<AKM, BKM, false, 128>), grid, dim3(256), 0, st, p);
     }
@@ -724,34 +727,31 @@ long plan_slices(int M, int N, int K, bool can_split, int compact, bool* big_out
     return s;
 }
 
-// images -> C.  a_km / b_km: the operand image is k-major ([k][row]) instead of k-contiguous ([row][k]).
-// Images are padded to multiples of 256 in both dimensions (ft_bf16_image), so either tile height may run off the logical M.
-int run_images(const unsigned short* A, long lda, int a_km, const unsigned short* B, long ldb, int b_km, float* C, long ldc,
-               const float* bias, int M, int N, int K, float alpha, float beta, int act, int flags, hipStream_t st,
-               const int* rowmap = nullptr, const int* rows_dev = nullptr, int compact = 0, int k_shift = 0,
-               const float* r1row = nullptr, const float* r1col = nullptr, float* split_work = nullptr, size_t split_work_bytes = 0,
-               const int* a_rows = nullptr) {
-    BfP p;
-    p.a_rows = a_rows;
-    p.A = A; p.B = B; p.C = C; p.bias = bias;
-    p.M = M; p.N = N; p.nk = cdiv(K, 32); p.lda = lda; p.ldb = ldb; p.ldc = ldc;
-    p.alpha = alpha; p.beta = beta; p.act = act;
-    p.rowmap = rowmap; p.rows_dev = rows_dev; p.compact = compact; p.k_shift = k_shift;
-    p.r1row = r1row; p.r1col = r1col;
-    p.c_slice = 0;
-    p.c16 = (flags & FT_GEMM_C16) ? 1 : 0;
-    if (p.c16 && (beta != 0.f || (flags & (FT_GEMM_SPLITK | FT_GEMM_SPLITK_DET))))
+// What a call will run, decided from the host-side arguments alone (no launch, no device access): the one place that turns a shape into
+// a kernel instantiation and a grid.  run_images launches exactly this; ft_gemm_img_plan reports it.
+struct ImgPlan {
+    bool big, wide, det_on;                 // 256-row tile; 64-wide single-buffer stages; deterministic split-K in effect
+    bool atomics;                           // atomic epilogue (deterministic split-K runs the store epilogue, one C slice per k-slice)
+    KernelSel sel;                          // the instantiation those select
+    int gx, gy, ksteps, splits, chunk_w, gridx, vec_c, c16;
+};
+int plan_images(const float* C, long ldc, int a_km, int b_km, int M, int N, int K, float beta, int act, int flags, int compact, bool r1,
+                const void* split_work, size_t split_work_bytes, bool a_rows, ImgPlan* pl) {
+    pl->c16 = (flags & FT_GEMM_C16) ? 1 : 0;
+    if (pl->c16 && (beta != 0.f || (flags & (FT_GEMM_SPLITK | FT_GEMM_SPLITK_DET))))
         return ft_fail(FT_EINVAL, "ft_gemm_img: FT_GEMM_C16 takes beta == 0 and no split-K");
     // deterministic split-K: the slices' partial products side by side in a workspace + a fixed-order reduction (for FORWARD GEMMs
     // with few output tiles and a long K: a forward pass must be a function of its inputs, which the atomics' order is not)
-    const bool det = (flags & FT_GEMM_SPLITK_DET) && split_work && act == FT_ACT_NONE && beta == 0.f && compact == 0 && !r1row && K >= 2048 &&
+    const bool det = (flags & FT_GEMM_SPLITK_DET) && split_work && act == FT_ACT_NONE && beta == 0.f && compact == 0 && !r1 && K >= 2048 &&
                      N % 4 == 0 && ldc % 4 == 0 && reinterpret_cast<uintptr_t>(C) % 16 == 0 && reinterpret_cast<uintptr_t>(split_work) % 16 == 0;
-    const bool can_split = det || ((flags & FT_GEMM_SPLITK) && act == FT_ACT_NONE && (beta == 0.f || beta == 1.f) && K >= 2048 && !r1row);
+    const bool can_split = det || ((flags & FT_GEMM_SPLITK) && act == FT_ACT_NONE && (beta == 0.f || beta == 1.f) && K >= 2048 && !r1);
     bool big;
     long s = plan_slices(M, N, K, can_split, compact, &big);
     const int RTA = big ? 256 : TB;
-    p.gx = cdiv(N, TB); p.gy = cdiv(M, RTA);
-    p.vec_c = (reinterpret_cast<uintptr_t>(C) % 16 == 0 && ldc % 4 == 0) ? 1 : 0;      // (16-bit C: 8-byte pieces of rows that start 8-byte aligned)
+    const int nk = cdiv(K, 32);
+    pl->big = big;
+    pl->gx = cdiv(N, TB); pl->gy = cdiv(M, RTA);
+    pl->vec_c = (reinterpret_cast<uintptr_t>(C) % 16 == 0 && ldc % 4 == 0) ? 1 : 0;      // (16-bit C: 8-byte pieces of rows that start 8-byte aligned)
     if (det) {                                   // as many slices as the workspace holds
         const long fit = (long)(split_work_bytes / ((size_t)M * N * sizeof(float)));
         if (s > fit) s = fit;
@@ -765,31 +765,64 @@ int run_images(const unsigned short* A, long lda, int a_km, const unsigned short
     // (the 256^2 kernels: 748), K 1024: 635 -> 599 -> 789, d[R,4096] W[4096,1664] (dX) 730 -> 884 -> 967, N = 1024 dense layers
     // 580-600 -> 690-700.  FT_GEMM_BF16_WIDE=0 (A/B hook, read per call): 32-wide stages everywhere
     const char* wide_env = getenv("FT_GEMM_BF16_WIDE");
-    const bool wide = (!wide_env || atoi(wide_env) != 0) && (p.nk & 1) == 0 && !(a_km && b_km) && !big;
-    p.ksteps = cdiv(p.nk, s);
-    if (wide && (p.ksteps & 1)) ++p.ksteps;            // (k-slices of whole 64-wide stages)
-    p.splits = cdiv(p.nk, p.ksteps);
-    if (a_rows && (!wide || p.splits != 1))
+    pl->wide = (!wide_env || atoi(wide_env) != 0) && (nk & 1) == 0 && !(a_km && b_km) && !big;
+    pl->ksteps = cdiv(nk, s);
+    if (pl->wide && (pl->ksteps & 1)) ++pl->ksteps;            // (k-slices of whole 64-wide stages)
+    pl->splits = cdiv(nk, pl->ksteps);
+    if (a_rows && (!pl->wide || pl->splits != 1))
         return ft_fail(FT_EINVAL, "ft_gemm_img: a_rows is read by the 64-wide single-buffer kernel only (FT_GEMM_BF16_WIDE=0 / FT_GEMM_BF16_TILE=256 exclude it)");
-    const bool det_on = det && p.splits > 1;
+    pl->det_on = det && pl->splits > 1;
+    pl->atomics = pl->splits > 1 && !pl->det_on;
+    // (the atomic kernels and the 256-row tile have 32-wide stages only; `wide` is false for k-major x k-major and for the tall tile, and a
+    //  row list was refused above unless the call is wide and un-split)
+    pl->sel.tile_rows = big ? 256 : TB;
+    pl->sel.atomics = pl->atomics ? 1 : 0;
+    pl->sel.stage_k = (pl->wide && !pl->atomics) ? 64 : 32;
+    pl->sel.gather = (a_rows && pl->sel.stage_k == 64) ? 1 : 0;
+    // L2-aware tile order for the un-split kernels: column chunks whose B panels (chunk_w x TB rows x K) fit ~2 MB of an XCD's L2
+    static const int order_on = [] { const char* e = getenv("FT_GEMM_BF16_ORDER"); return e ? atoi(e) : 1; }();
+    pl->chunk_w = 0;
+    pl->gridx = pl->gx * pl->gy;
+    if (order_on && pl->splits == 1 && pl->gy >= 16) {
+        long cw = (2l << 20) / ((long)TB * (long)nk * 32 * 2);
+        pl->chunk_w = (int)(cw < 1 ? 1 : (cw > pl->gx ? pl->gx : cw));
+        pl->gridx = 8 * ((pl->gy + 7) / 8) * pl->gx;          // every XCD is handed the blocks of the largest row range
+    }
+    return FT_OK;
+}
+
+// images -> C.  a_km / b_km: the operand image is k-major ([k][row]) instead of k-contiguous ([row][k]).
+// Images are padded to multiples of 256 in both dimensions (ft_bf16_image), so either tile height may run off the logical M.
+int run_images(const unsigned short* A, long lda, int a_km, const unsigned short* B, long ldb, int b_km, float* C, long ldc,
+               const float* bias, int M, int N, int K, float alpha, float beta, int act, int flags, hipStream_t st,
+               const int* rowmap = nullptr, const int* rows_dev = nullptr, int compact = 0, int k_shift = 0,
+               const float* r1row = nullptr, const float* r1col = nullptr, float* split_work = nullptr, size_t split_work_bytes = 0,
+               const int* a_rows = nullptr) {
+    ImgPlan pl;
+    const int prc = plan_images(C, ldc, a_km, b_km, M, N, K, beta, act, flags, compact, r1row != nullptr, split_work, split_work_bytes,
+                                a_rows != nullptr, &pl);
+    if (prc != FT_OK) return prc;
+    BfP p;
+    p.a_rows = a_rows;
+    p.A = A; p.B = B; p.C = C; p.bias = bias;
+    p.M = M; p.N = N; p.nk = cdiv(K, 32); p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.alpha = alpha; p.beta = beta; p.act = act;
+    p.rowmap = rowmap; p.rows_dev = rows_dev; p.compact = compact; p.k_shift = k_shift;
+    p.r1row = r1row; p.r1col = r1col;
+    p.c_slice = 0;
+    p.c16 = pl.c16;
+    p.gx = pl.gx; p.gy = pl.gy; p.vec_c = pl.vec_c;
+    p.ksteps = pl.ksteps; p.splits = pl.splits; p.chunk_w = pl.chunk_w;
+    const bool det_on = pl.det_on;
     if (det_on) {
         p.C = split_work; p.ldc = N; p.c_slice = (long)M * N; p.bias = nullptr;
         p.vec_c = 1;
     } else if (p.splits > 1 && beta == 0.f) {
         FT_CHECK_HIP(hipMemset2DAsync(C, sizeof(float) * ldc, 0, sizeof(float) * N, M, st));
     }
-    // L2-aware tile order for the un-split kernels: column chunks whose B panels (chunk_w x TB rows x K) fit ~2 MB of an XCD's L2
-    static const int order_on = [] { const char* e = getenv("FT_GEMM_BF16_ORDER"); return e ? atoi(e) : 1; }();
-    p.chunk_w = 0;
-    int gridx = p.gx * p.gy;
-    if (order_on && p.splits == 1 && p.gy >= 16) {
-        long cw = (2l << 20) / ((long)TB * (long)p.nk * 32 * 2);
-        p.chunk_w = (int)(cw < 1 ? 1 : (cw > p.gx ? p.gx : cw));
-        gridx = 8 * ((p.gy + 7) / 8) * p.gx;          // every XCD is handed the blocks of the largest row range
-    }
-    const dim3 grid(gridx, p.splits);
-    if (a_km) { if (b_km) launch_s<true, true>(p, grid, big, wide, st); else launch_s<true, false>(p, grid, big, wide, st); }
-    else      { if (b_km) launch_s<false, true>(p, grid, big, wide, st); else launch_s<false, false>(p, grid, big, wide, st); }
+    const dim3 grid(pl.gridx, p.splits);
+    if (a_km) { if (b_km) launch_s<true, true>(p, grid, pl.sel, st); else launch_s<true, false>(p, grid, pl.sel, st); }
+    else      { if (b_km) launch_s<false, true>(p, grid, pl.sel, st); else launch_s<false, false>(p, grid, pl.sel, st); }
     if (det_on) {
         const long n4 = ((long)M * N) >> 2;
         const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
@@ -798,6 +831,24 @@ int run_images(const unsigned short* A, long lda, int a_km, const unsigned short
     FT_CHECK_LAUNCH();
     return FT_OK;
 }
+
+// the argument rules of ft_gemm_img, shared with ft_gemm_img_plan (`who`: the entry point the message names, as FT_CHECK_ARG would)
+#define IMG_CHECK_ARG(cond)                                                           \
+    do {                                                                              \
+        if (!(cond)) return ft_fail(FT_EINVAL, "%s: invalid argument: %s", who, #cond); \
+    } while (0)
+int check_img_args(const ft_gemm_img_args* a, const char* who) {
+    IMG_CHECK_ARG(a != nullptr);
+    IMG_CHECK_ARG(a->A && a->B && a->C && a->M >= 1 && a->N >= 1 && a->K >= 1);
+    IMG_CHECK_ARG(a->lda % 8 == 0 && a->ldb % 8 == 0 && reinterpret_cast<uintptr_t>(a->A) % 16 == 0 && reinterpret_cast<uintptr_t>(a->B) % 16 == 0);
+    IMG_CHECK_ARG(a->compact >= 0 && a->compact <= 2 && (a->compact == 0 || a->rows_dev) && (a->compact != 1 || a->rowmap));
+    IMG_CHECK_ARG(a->k_shift >= 0 && (a->compact == 2 || a->k_shift == 0));
+    IMG_CHECK_ARG((a->r1_row == nullptr) == (a->r1_col == nullptr));
+    // row gather of A: the 64-wide single-buffer store kernel's conditions
+    IMG_CHECK_ARG(a->a_rows == nullptr || (a->compact == 1 && a->a_kmajor == 0 && !(a->flags & (FT_GEMM_SPLITK | FT_GEMM_SPLITK_DET)) && a->K % 64 == 0));
+    return FT_OK;
+}
+#undef IMG_CHECK_ARG
 
 bool qualifies(const ft_gemm_args* a) {
     return a->mode == FT_OP16 && a->batch == 1 && a->M >= 32 && a->N >= 32 && a->K >= 16 &&
@@ -1040,17 +1091,28 @@ extern "C" size_t ft_gemm_img_split_work_bytes(int M, int N, int K) {
     const long s = plan_slices(M, N, K, true, 0, &big);
     return s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
 }
+
+// what ft_gemm_img(a) would launch (plan_images, the launcher's own decision); format-independent
+extern "C" int ft_gemm_img_plan(const ft_gemm_img_args* a, ft_gemm_img_plan_t* out) {
+    if (const int rc = check_img_args(a, __func__)) return rc;
+    FT_CHECK_ARG(out != nullptr);
+    ImgPlan pl;
+    const int rc = plan_images(a->C, a->ldc, a->a_kmajor, a->b_kmajor, a->M, a->N, a->K, a->beta, a->act, a->flags, a->compact,
+                               a->r1_row != nullptr, a->split_work, a->split_work_bytes, a->a_rows != nullptr, &pl);
+    if (rc != FT_OK) return rc;
+    out->tile_rows = pl.sel.tile_rows;
+    out->stage_k = pl.sel.stage_k;
+    out->gather = pl.sel.gather;
+    out->atomics = pl.sel.atomics;
+    out->det = pl.det_on ? 1 : 0;
+    out->splits = pl.splits;
+    out->chunk_w = pl.chunk_w;
+    return FT_OK;
+}
 #endif
 
 extern "C" int FT_OPNAME(ft_gemm_img)(const ft_gemm_img_args* a, void* stream) {
-    FT_CHECK_ARG(a != nullptr);
-    FT_CHECK_ARG(a->A && a->B && a->C && a->M >= 1 && a->N >= 1 && a->K >= 1);
-    FT_CHECK_ARG(a->lda % 8 == 0 && a->ldb % 8 == 0 && reinterpret_cast<uintptr_t>(a->A) % 16 == 0 && reinterpret_cast<uintptr_t>(a->B) % 16 == 0);
-    FT_CHECK_ARG(a->compact >= 0 && a->compact <= 2 && (a->compact == 0 || a->rows_dev) && (a->compact != 1 || a->rowmap));
-    FT_CHECK_ARG(a->k_shift >= 0 && (a->compact == 2 || a->k_shift == 0));
-    FT_CHECK_ARG((a->r1_row == nullptr) == (a->r1_col == nullptr));
-    // row gather of A: the 64-wide single-buffer store kernel's conditions
-    FT_CHECK_ARG(a->a_rows == nullptr || (a->compact == 1 && a->a_kmajor == 0 && !(a->flags & (FT_GEMM_SPLITK | FT_GEMM_SPLITK_DET)) && a->K % 64 == 0));
+    if (const int rc = check_img_args(a, __func__)) return rc;
     return run_images(reinterpret_cast<const unsigned short*>(a->A), a->lda, a->a_kmajor, reinterpret_cast<const unsigned short*>(a->B),
                       a->ldb, a->b_kmajor, a->C, a->ldc, a->bias, a->M, a->N, a->K, a->alpha, a->beta, a->act, a->flags,
                       reinterpret_cast<hipStream_t>(stream), a->rowmap, a->rows_dev, a->compact, a->k_shift, a->r1_row, a->r1_col,

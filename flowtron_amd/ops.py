@@ -306,18 +306,16 @@ def images_apply(mode, M, N, K):
     return _BF16_IMAGES and L.is16(mode) and M >= 32 and N >= 32 and K >= 16 and M * N * K >= (1 << 20)
 
 
-def gemm_img(A, a_km, a_ptr, B, b_km, b_ptr, Cm, M, N, K, ldc, bias=None, act=L.ACT_NONE, alpha=1.0, beta=0.0, splitk=False,
-             rowmap=None, compact=0, k_shift=0, rank1=None, c16=False, a_rows=None):
-    """C[M,N] = act(alpha * A.B + beta*C + bias) from images.  a_ptr / b_ptr: A.ptr(...) / B.ptr(...) (may point inside).
-    rowmap + compact: 1 = M runs over the map's compact rows (pass M = rowmap.cap), C rows are scattered through the map;
-    2 = the reduction runs over compact rows (pass K = rowmap.cap; k_shift = a row shift already applied to a_ptr).
-    rank1 = (r [C rows] fp32, c_ptr -> N floats): C[row][col] += r[row] * c[col] in the epilogue (row = the output row).
-    a_rows (int32 device list, compact = 1): compact row m reads row a_rows[m] of A's image instead of row m."""
+def _gemm_img_args(A, a_km, a_ptr, B, b_km, b_ptr, Cm, M, N, K, ldc, bias=None, act=L.ACT_NONE, alpha=1.0, beta=0.0, splitk=False,
+                   rowmap=None, compact=0, k_shift=0, rank1=None, c16=False, a_rows=None, split_work_bytes=None):
+    """the ft_gemm_img_args of gemm_img's arguments, and the split-K workspace they point into (to be kept alive by the caller)"""
     L.require_cuda(Cm, bias)
     flags, work, need = (L.GEMM_SPLITK if splitk else 0), None, 0
     if splitk == "det":
         # deterministic split-K (forward GEMMs): partial products side by side in a workspace, added in a fixed order
         need = L.lib().ft_gemm_img_split_work_bytes(M, N, K)
+        if split_work_bytes is not None:         # a smaller workspace than asked for: the call runs as many slices as it holds
+            need = min(need, int(split_work_bytes))
         flags = L.GEMM_SPLITK_DET if need else 0
         work = torch.empty(need, device=Cm.device, dtype=torch.uint8) if need else None
     if c16:                                      # C is a 16-bit tensor of the operands' format (FT_GEMM_C16)
@@ -330,7 +328,28 @@ def gemm_img(A, a_km, a_ptr, B, b_km, b_ptr, Cm, M, N, K, ldc, bias=None, act=L.
                       L.ptr(rank1[0]) if rank1 is not None else None, rank1[1] if rank1 is not None else None,
                       L.ptr(work), need, L.ptr(a_rows) if a_rows is not None else None)
     assert A.fmt == B.fmt, "operand images of different formats"
+    return a, work
+
+
+def gemm_img(A, a_km, a_ptr, B, b_km, b_ptr, Cm, M, N, K, ldc, **kw):
+    """C[M,N] = act(alpha * A.B + beta*C + bias) from images.  a_ptr / b_ptr: A.ptr(...) / B.ptr(...) (may point inside).
+    Keywords: bias, act, alpha, beta, splitk (True: atomic split-K allowed; "det": the deterministic form, split_work_bytes = a
+    smaller workspace than the library asks for), c16 (Cm is a 16-bit tensor of the operands' format), and
+    rowmap + compact: 1 = M runs over the map's compact rows (pass M = rowmap.cap), C rows are scattered through the map;
+    2 = the reduction runs over compact rows (pass K = rowmap.cap; k_shift = a row shift already applied to a_ptr).
+    rank1 = (r [C rows] fp32, c_ptr -> N floats): C[row][col] += r[row] * c[col] in the epilogue (row = the output row).
+    a_rows (int32 device list, compact = 1): compact row m reads row a_rows[m] of A's image instead of row m."""
+    a, _work = _gemm_img_args(A, a_km, a_ptr, B, b_km, b_ptr, Cm, M, N, K, ldc, **kw)
     L.check(L.op16("ft_gemm_img", A.fmt)(C.byref(a), L.stream()), "ft_gemm_img")
+
+
+def gemm_img_plan(A, a_km, a_ptr, B, b_km, b_ptr, Cm, M, N, K, ldc, **kw):
+    """what gemm_img would launch with the same arguments (ft_gemm_img_plan: the launcher's own decision, nothing is launched):
+    a GemmImgPlan (tile_rows, stage_k, gather, atomics, det, splits, chunk_w)"""
+    a, _work = _gemm_img_args(A, a_km, a_ptr, B, b_km, b_ptr, Cm, M, N, K, ldc, **kw)
+    plan = L.GemmImgPlan()
+    L.check(L.lib().ft_gemm_img_plan(C.byref(a), C.byref(plan)), "ft_gemm_img_plan")
+    return plan
 
 
 # hand-off of an output-gradient image between two autograd nodes of the SAME backward pass (the LSTM backward builds the

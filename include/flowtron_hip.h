@@ -66,11 +66,12 @@
 extern "C" {
 #endif
 
-#define FT_ABI_VERSION 14
+#define FT_ABI_VERSION 15
 /* (ft_gemm_img_args grew its trailing a_rows field and ft_chunk_gather_rows was added WITHOUT a new number: 14 therefore names two struct
  * layouts, and a caller's ft_abi_version() check cannot tell a library built before the field from one built after it.  Callers zero-
  * initialise the struct and are built together with the library (flowtron_amd/build.py rebuilds on any header change); a binding kept
- * outside this tree must be rebuilt against this header.) */
+ * outside this tree must be rebuilt against this header.)
+ * 15: ft_gemm_img_plan. */
 
 enum { FT_OK = 0, FT_EINVAL = -1, FT_EHIP = -2, FT_EUNSUPPORTED = -3 };
 enum { FT_F32 = 0, FT_BF16 = 1, FT_F16 = 2 };
@@ -152,6 +153,16 @@ typedef struct {
     const int32_t* a_rows;
 } ft_gemm_img_args;
 size_t ft_gemm_img_split_work_bytes(int M, int N, int K);
+/* ABI 15: what ft_gemm_img(a) / ft_gemm_img_f16(a) would launch, decided by the launcher's own code -- no launch, no device access (the
+ * pointers are only looked at for NULL and alignment).  Same return codes as the call itself for arguments it would refuse.  One of the
+ * tile forms of the kernel: tile_rows x 128 outputs per workgroup; stage_k = 64: the single-buffer form with 64-wide k stages; gather: A's
+ * rows through a_rows; atomics: split-K with fp32 atomics; det: split-K through split_work and the fixed-order reduction; splits = k-slices
+ * launched (compact = 2: the kernel divides the rows the batch has over them); chunk_w > 0: the L2-aware tile order with column chunks of
+ * that many tiles.  Lets a test assert which path a shape reaches. */
+typedef struct { int tile_rows;      /* 128 | 256 */
+                 int stage_k;        /* 32 | 64 (64 = single-buffer form) */
+                 int gather, atomics, det, splits, chunk_w; } ft_gemm_img_plan_t;
+int ft_gemm_img_plan(const ft_gemm_img_args* a, ft_gemm_img_plan_t* out);
 size_t ft_bf16_image_bytes(int64_t rows, int64_t cols);
 int ft_bf16_image(const float* src, int64_t ld, int64_t rows, int64_t cols, void* dst, void* stream);
 /* the same image plus colsum[c] = sum_r src[r][c] in fp32 (bias gradients ride on the conversion pass of the output

@@ -215,7 +215,7 @@ def test_equal_rates_and_abi(monkeypatch):
     assert torch.equal(y[0], x[0]) and (y[2, 1:] == 0).all()
     assert calls["ft_resample_ragged"] == 0
     h = ctypes.CDLL(L.LIB_PATH)
-    assert h.ft_abi_version() == 14
+    assert h.ft_abi_version() == 15
     assert hasattr(h, "ft_resample_ragged") and hasattr(h, "ft_resample_out_len")
     # the C entry refuses a table it cannot hold, with a message, before any launch
     rc = L.lib().ft_resample_ragged(L.ptr(x), None, L.ptr(x), L.ptr(x), L.ptr(x), 1, 500, 500, 22050, 22051, 13, L.stream())

@@ -13,6 +13,7 @@
 //              lane <-> a) that recomputes tanh once and produces dQ (plain stores), dK (one fp32
 //              atomic per (l, a) per 32-row tile) and dv.
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
@@ -32,78 +33,106 @@ __device__ __forceinline__ float rsig(float x) { return __builtin_amdgcn_rcpf(__
 // |q'|, |k'| <= EXP_SAFE (|q|, |k| <= 20.8: both factors and their product stay finite and normal); a tile that holds a larger
 // value -- decided on the data -- takes the sum form above, so the result never depends on a range assumption.
 constexpr float EXP_SAFE = 60.0f;
-__device__ __forceinline__ float rsig_prod(float eq, float ek) { return __builtin_amdgcn_rcpf(fmaf(eq, ek, 1.0f)); }
-template <bool PROD>
-__device__ __forceinline__ float rs(float q, float k) {
-    if constexpr (PROD) return rsig_prod(q, k);
-    else return rsig(q + k);
-}
 
 // scores of one a-chunk for a 4x4 (t, l) micro-tile (UNI: one query row only); qs / ks hold q', k' (sum form) or 2^q', 2^k' (PROD).
 // PROD form with PACKED fp32 math (round 6): the two non-transcendental operations per element -- Eq Ek + 1 and acc += v r -- run as
 // v_pk_fma_f32 on the (x, y) / (z, w) halves of the staged float4s, the accumulators as (even a, odd a) pairs that are added once at
 // the end of the chunk: 2 packed instructions per 4 elements instead of 8 scalar ones beside the 4 v_rcp_f32 (0.556 -> 0.529 ms per
-// call at the bench shape: the pass is stall-bound at two waves per SIMD -- 239 VGPRs, 64 KB of LDS --, VALU busy 44 %,
-// profiles/r06_pmc_VALU_TRANS.json; the backward pass, VALU busy 71 %, gains more from the same change).
+// call at the bench shape, profiles/r06_pmc_VALU_TRANS.json; the backward pass gains more from the same change).
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-template <bool PROD, bool UNI>
-__device__ __forceinline__ void score_chunk(const float* qs, const float* ks, const float* vs, int tg, int tl, const bool (&jact)[4],
-                                            float (&acc)[4][4], float& vsum, int LDAs, int ACs) {
-    if constexpr (PROD) {
-        f32x2 acc2[4][4];
+// NJ = number of active 32-key groups of this key pass (groups 0 .. NJ-1: a prefix, uniform per workgroup), a compile-time constant so
+// that the a4 body is one straight basic block.  The LDS operands are SOFTWARE-PIPELINED a whole iteration ahead: the v, q and key
+// fragments of iteration a4 + 1 are issued before the arithmetic of iteration a4 (4 + 4 NI + 4 NJ registers in flight), so that no
+// ds_read is waited for behind its own issue -- at two waves per SIMD there is next to nothing else to cover an LDS round trip.
+// The last iteration's prefetch reads the four pad columns of its rows (LDA = AC + 4) and the four floats behind vs (es[0..3]): inside
+// the workgroup's LDS, never used.  Arithmetic and summation order per accumulator: a4 ascending, the (x, y) pair before the (z, w)
+// pair, one acc2.x + acc2.y per chunk.
+// (the compiler folds a loop-carried fragment back into a load at the top of the next iteration -- a phi of loads becomes a load of a
+// phi of addresses -- which puts the wait straight behind the issue again; an empty asm that "rewrites" the registers at the end of
+// the iteration makes the carried value something it cannot re-load)
+__device__ __forceinline__ void pin(f32x4& f) { asm volatile("" : "+v"(f)); }
+template <int NI, int NJ>
+struct ScoreFrag {
+    f32x4 v, q[NI], k[NJ];
+};
+template <bool PROD, bool UNI, int NJ>
+__device__ __forceinline__ void score_chunk(const float* qs, const float* ks, const float* vs, int tg, int tl, f32x4 (&acc)[4], float& vsum) {
+    constexpr int NI = UNI ? 1 : 4, NA4 = AC / 4;
+    const float* qp = qs + (UNI ? 0 : tg * 4) * LDA;
+    const float* kp = ks + tl * LDA;
+    auto fetch = [&](ScoreFrag<NI, NJ>& f, int a4) {
+        f.v = *reinterpret_cast<const f32x4*>(vs + a4 * 4);
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < NI; ++i) f.q[i] = *reinterpret_cast<const f32x4*>(qp + i * LDA + a4 * 4);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc2[i][j] = (f32x2){0.f, 0.f};
-        const f32x2 one = {1.f, 1.f};
+        for (int j = 0; j < NJ; ++j) f.k[j] = *reinterpret_cast<const f32x4*>(kp + j * 32 * LDA + a4 * 4);
+    };
+    f32x2 acc2[NI][NJ];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc2[i][j] = (f32x2){0.f, 0.f};
+    const f32x2 one = {1.f, 1.f};
+    ScoreFrag<NI, NJ> cur;
+    fetch(cur, 0);
 #pragma unroll 2
-        for (int a4 = 0; a4 < ACs / 4; ++a4) {
-            const float4 vv = *reinterpret_cast<const float4*>(vs + a4 * 4);
-            vsum += (vv.x + vv.y) + (vv.z + vv.w);
-            const f32x2 v01 = {vv.x, vv.y}, v23 = {vv.z, vv.w};
-            float4 q[4];
-#pragma unroll
-            for (int i = 0; i < (UNI ? 1 : 4); ++i) q[i] = *reinterpret_cast<const float4*>(qs + ((UNI ? 0 : tg * 4) + i) * LDAs + a4 * 4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (jact[j]) {
-                    const float4 kk = *reinterpret_cast<const float4*>(ks + (j * 32 + tl) * LDAs + a4 * 4);
-                    const f32x2 k01 = {kk.x, kk.y}, k23 = {kk.z, kk.w};
-#pragma unroll
-                    for (int i = 0; i < (UNI ? 1 : 4); ++i) {
-                        const f32x2 d01 = pk_fma((f32x2){q[i].x, q[i].y}, k01, one), d23 = pk_fma((f32x2){q[i].z, q[i].w}, k23, one);
-                        const f32x2 r01 = {__builtin_amdgcn_rcpf(d01.x), __builtin_amdgcn_rcpf(d01.y)};
-                        const f32x2 r23 = {__builtin_amdgcn_rcpf(d23.x), __builtin_amdgcn_rcpf(d23.y)};
-                        acc2[i][j] = pk_fma(v23, r23, pk_fma(v01, r01, acc2[i][j]));
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < (UNI ? 1 : 4); ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] += acc2[i][j].x + acc2[i][j].y;
-        return;
-    }
-#pragma unroll 2
-    for (int a4 = 0; a4 < ACs / 4; ++a4) {
-        const float4 vv = *reinterpret_cast<const float4*>(vs + a4 * 4);
+    for (int a4 = 0; a4 < NA4; ++a4) {
+        ScoreFrag<NI, NJ> nxt;
+        fetch(nxt, a4 + 1);
+        __builtin_amdgcn_sched_barrier(0);              // the prefetch stays above this iteration's arithmetic ...
+        const f32x4 vv = cur.v;
         vsum += (vv.x + vv.y) + (vv.z + vv.w);
-        float4 q[4];
+        if constexpr (PROD) {
 #pragma unroll
-        for (int i = 0; i < (UNI ? 1 : 4); ++i) q[i] = *reinterpret_cast<const float4*>(qs + ((UNI ? 0 : tg * 4) + i) * LDAs + a4 * 4);
+            for (int j = 0; j < NJ; ++j) {
+                const f32x4 kk = cur.k[j];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (jact[j]) {
-                const float4 kk = *reinterpret_cast<const float4*>(ks + (j * 32 + tl) * LDAs + a4 * 4);
+                for (int i = 0; i < NI; ++i) {
+                    const f32x4 q = cur.q[i];
+                    const f32x2 d01 = pk_fma(q.xy, kk.xy, one), d23 = pk_fma(q.zw, kk.zw, one);
+                    const f32x2 r01 = {__builtin_amdgcn_rcpf(d01.x), __builtin_amdgcn_rcpf(d01.y)};
+                    const f32x2 r23 = {__builtin_amdgcn_rcpf(d23.x), __builtin_amdgcn_rcpf(d23.y)};
+                    acc2[i][j] = pk_fma(vv.zw, r23, pk_fma(vv.xy, r01, acc2[i][j]));
+                }
+            }
+        } else {
 #pragma unroll
-                for (int i = 0; i < (UNI ? 1 : 4); ++i) {
-                    acc[i][j] += vv.x * rs<PROD>(q[i].x, kk.x) + vv.y * rs<PROD>(q[i].y, kk.y) +
-                                 vv.z * rs<PROD>(q[i].z, kk.z) + vv.w * rs<PROD>(q[i].w, kk.w);
+            for (int j = 0; j < NJ; ++j) {
+                const f32x4 kk = cur.k[j];
+#pragma unroll
+                for (int i = 0; i < NI; ++i) {
+                    const f32x4 q = cur.q[i];
+                    // rounding pinned: one rounded product, three FMAs (left to -ffp-contract, which of the four products is
+                    // rounded on its own differs from row to row and between the unrolled copies of this loop)
+                    acc[i][j] += fmaf(vv.w, rsig(q.w + kk.w), fmaf(vv.z, rsig(q.z + kk.z), fmaf(vv.x, rsig(q.x + kk.x), __fmul_rn(vv.y, rsig(q.y + kk.y)))));
                 }
             }
         }
+        __builtin_amdgcn_sched_barrier(0);              // ... and its wait below it
+        cur = nxt;
+        pin(cur.v);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) pin(cur.q[i]);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) pin(cur.k[j]);
+    }
+    if constexpr (PROD) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) acc[i][j] += acc2[i][j].x + acc2[i][j].y;
+    }
+}
+
+// calls f with the number of active key groups (1 .. 4) as a compile-time constant
+template <class F>
+__device__ __forceinline__ void with_nj(int nj, F&& f) {
+    switch (nj) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
     }
 }
 
@@ -147,64 +176,74 @@ __global__ __launch_bounds__(256) void attn_fwd_k(const float* __restrict__ Q, c
     const bool idle = uniform_q && tg != 0;              // row groups 1..7 have nothing to compute in a uniform tile
 
     for (int lt = 0; lt < nlt; ++lt) {
-        float acc[4][4];
+        f32x4 acc[4];                    // [i][j]: query row i of this thread's four, key group j
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-        bool jact[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) jact[j] = (lt * LT + j * 32) < len;
+        for (int i = 0; i < 4; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        // key groups 0 .. nj-1 of this pass hold a key below len (a prefix; nlt makes nj >= 1): uniform per workgroup and key pass
+        const int nj = min(4, (len - lt * LT + 31) / 32);
         float vsum = 0.f;
+        // the inner loops are instantiated per nj; the staging code around them exists once (a copy of it per nj has the compiler
+        // hoist four sets of its addresses: 350 spilled SGPRs and one wave per SIMD)
+        auto scores = [&](auto prod_c, auto uni_c) {
+            with_nj(nj, [&](auto njc) { score_chunk<decltype(prod_c)::value, decltype(uni_c)::value, decltype(njc)::value>(qs, ks, vs, tg, tl, acc, vsum); });
+        };
 
         for (int a0 = 0; a0 < A; a0 += AC) {
-            // load the chunk into registers first (no LDS touched yet), decide the form on the data, then stage
+            // load the chunk into registers first (no LDS touched yet), decide the form on the data, then stage.  The loads are
+            // UNCONDITIONAL, from clamped indices, and the bounds select the value afterwards: a load under `t < T && a < A` is a
+            // branch of its own with its wait inside it -- 40 global round trips per chunk, one after the other
+            // (the thread index is made opaque per chunk: the ~50 global and LDS staging addresses are then formed here, per chunk,
+            // and not hoisted out of the a-chunk loop, where they would sit in ~80 registers across the score loops)
+            int st = tid;
+            asm volatile("" : "+v"(st));
             float qv[(TT * AC) / 256], kv[(LT * AC) / 256];
             bool big = false;
 #pragma unroll
             for (int r = 0; r < (TT * AC) / 256; ++r) {
-                const int idx = tid + 256 * r;
+                const int idx = st + 256 * r;
                 const int row = idx >> 6, col = idx & 63;
                 const int t = t0 + row, a = a0 + col;
-                qv[r] = (t < T && a < A) ? C2 * Q[((long)t * B + b) * A + a] : 0.f;
+                const float x = Q[((long)min(t, T - 1) * B + b) * A + min(a, A - 1)];
+                qv[r] = (t < T && a < A) ? C2 * x : 0.f;
                 big |= !(fabsf(qv[r]) <= EXP_SAFE);
             }
 #pragma unroll
             for (int r = 0; r < (LT * AC) / 256; ++r) {
-                const int idx = tid + 256 * r;
+                const int idx = st + 256 * r;
                 const int row = idx >> 6, col = idx & 63;
                 const int l = lt * LT + row, a = a0 + col;
-                kv[r] = (l < len && a < A) ? C2 * K[((long)l * B + b) * A + a] : 0.f;
+                const float x = K[((long)min(l, len - 1) * B + b) * A + min(a, A - 1)];
+                kv[r] = (l < len && a < A) ? C2 * x : 0.f;
                 big |= !(fabsf(kv[r]) <= EXP_SAFE);
             }
             const bool prod = !__syncthreads_or(big ? 1 : 0);      // (also: the previous chunk's LDS reads are done)
 #pragma unroll
             for (int r = 0; r < (TT * AC) / 256; ++r) {
-                const int idx = tid + 256 * r;
+                const int idx = st + 256 * r;
                 qs[(idx >> 6) * LDA + (idx & 63)] = prod ? __builtin_amdgcn_exp2f(qv[r]) : qv[r];
             }
 #pragma unroll
             for (int r = 0; r < (LT * AC) / 256; ++r) {
-                const int idx = tid + 256 * r;
+                const int idx = st + 256 * r;
                 ks[(idx >> 6) * LDA + (idx & 63)] = prod ? __builtin_amdgcn_exp2f(kv[r]) : kv[r];
             }
-            if (tid < AC) vs[tid] = (a0 + tid < A) ? v[a0 + tid] : 0.f;
+            if (st < AC) vs[st] = (a0 + st < A) ? v[a0 + st] : 0.f;
             __syncthreads();
             if (uniform_q) {                                   // one score row (same summation order as the general path)
                 if (!idle) {
-                    if (prod) score_chunk<true, true>(qs, ks, vs, tg, tl, jact, acc, vsum, LDA, AC);
-                    else score_chunk<false, true>(qs, ks, vs, tg, tl, jact, acc, vsum, LDA, AC);
+                    if (prod) scores(std::true_type{}, std::true_type{});
+                    else scores(std::false_type{}, std::true_type{});
                 }
                 continue;
             }
-            if (prod) score_chunk<true, false>(qs, ks, vs, tg, tl, jact, acc, vsum, LDA, AC);
-            else score_chunk<false, false>(qs, ks, vs, tg, tl, jact, acc, vsum, LDA, AC);
+            if (prod) scores(std::true_type{}, std::false_type{});
+            else scores(std::false_type{}, std::false_type{});
         }
         if (uniform_q) {
             if (!idle) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    if (jact[j]) {
+                    if (j < nj) {
                         const float e = (vsum - 2.f * acc[0][j]) * inv_temp;
                         for (int r = 0; r < TT; ++r) es[r * LP + lt * LT + j * 32 + tl] = e;
                     }
@@ -215,7 +254,7 @@ __global__ __launch_bounds__(256) void attn_fwd_k(const float* __restrict__ Q, c
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                if (jact[j]) es[(tg * 4 + i) * LP + lt * LT + j * 32 + tl] = (vsum - 2.f * acc[i][j]) * inv_temp;
+                if (j < nj) es[(tg * 4 + i) * LP + lt * LT + j * 32 + tl] = (vsum - 2.f * acc[i][j]) * inv_temp;
     }
     __syncthreads();
 
@@ -321,7 +360,7 @@ __global__ __launch_bounds__(256) void attn_dqdk_k(const float* __restrict__ Q, 
                                                    const float* __restrict__ de, float* __restrict__ dQ, float* __restrict__ dK,
                                                    float* __restrict__ dv, int T, int B, int L, int A) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* de_s = smem;                 // [len][32]
+    float* de_s = smem;                 // [len][32], then [len] row sums
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int b = blockIdx.y, t0 = blockIdx.x * 32;
     const int len = min(in_lens[b], L);
@@ -342,13 +381,26 @@ __global__ __launch_bounds__(256) void attn_dqdk_k(const float* __restrict__ Q, 
                 if (t0 + i < T) dQ[((long)(t0 + i) * B + b) * A + a] = 0.f;
         return;
     }
+    // sum_t de[t][l] depends on (tile, l) only: formed once here, not by every wave for every key.  Association of the packed
+    // sums it replaces: (even t, odd t) pairs added in row order, then even + odd.
+    float* ds_s = de_s + len * 32;      // [len]
+    for (int l = tid; l < len; l += (int)blockDim.x) {
+        f32x2 ds2 = {0.f, 0.f};
+#pragma unroll
+        for (int i4 = 0; i4 < 8; ++i4) {
+            const float4 d4 = *reinterpret_cast<const float4*>(de_s + l * 32 + i4 * 4);
+            ds2 = ds2 + (f32x2){d4.x, d4.y} + (f32x2){d4.z, d4.w};
+        }
+        ds_s[l] = ds2.x + ds2.y;
+    }
+    __syncthreads();
     if (aw >= A) return;                // wave-uniform
     const int a = aw + lane;
     const bool av = a < A;
     const int ac = av ? a : A - 1;      // clamp: keeps the loads unconditional, results of idle lanes are dropped
     // rows in PAIRS (2 i, 2 i + 1): the non-transcendental arithmetic of an element -- Eq Ek + 1, u = r - r^2, dq += d u, dk += d u,
     // dv' += d r -- runs as v_pk_fma_f32 (round 6: five packed instructions per two elements where six scalar ones per element stood;
-    // sum_l,t d tanh = sum d - 2 sum d r, with sum d taken once per key from the de tile)
+    // sum_l,t d tanh = sum d - 2 sum d r, with sum d read once per key from ds_s)
     f32x2 eq2[16], dq2[16];
     bool qbig = false;
     auto qrow = [&](int i) { return C2 * Q[((long)min(t0 + i, T - 1) * B + b) * A + ac]; };     // (the rare sum-form path re-reads it: 32 registers less)
@@ -363,26 +415,40 @@ __global__ __launch_bounds__(256) void attn_dqdk_k(const float* __restrict__ Q, 
     const float* kp = K + (long)b * A + ac;
     const long ks = (long)B * A;
     const float va4 = 4.f * v[ac];
-    float kv_next = (len > 0) ? C2 * kp[0] : 0.f;
+    float* dkp_out = dK + (long)b * A + ac;
     const f32x2 one = {1.f, 1.f};
-    for (int l = 0; l < len; ++l) {
-        const float kv = kv_next;
-        if (l + 1 < len) kv_next = C2 * kp[(long)(l + 1) * ks];
-        float dkp = 0.f;
-        // product form (one v_rcp per element) unless this wave holds an out-of-range value for this key (wave-uniform choice)
-        if (!__any(qbig || !(fabsf(kv) <= EXP_SAFE))) {
+    // product form (one v_rcp per element) unless this wave holds an out-of-range value for this key (wave-uniform choice, per key,
+    // on the data).  Keys in ascending order; a RUN of product-form keys is a loop of its own, left for one sum-form key at a time,
+    // so that the product-form iteration keeps its 32 dq accumulators in place (one two-armed loop body copied all of them every key).
+    // The wait for k_next is a wait for every older vector-memory operation of the wave, atomics included, so a key's dK atomic is
+    // sent one key LATE, right behind the load at the top of the next iteration: by the time that load is waited for, both have had
+    // a whole iteration (the parent waited for an atomic and a load it had only just issued, every key).
+    float dk_prev = 0.f;
+    auto send_prev = [&](int ln) { if (av && ln > 0) atomicAdd(dkp_out + (long)(ln - 1) * ks, dk_prev); };
+    float kv = (len > 0) ? C2 * kp[0] : 0.f;
+    int l = 0;
+    while (l < len) {
+        while (!__any(qbig || !(fabsf(kv) <= EXP_SAFE))) {
+            // the next key's element, issued a whole iteration ahead of its use: unconditional (the last key re-reads itself) and
+            // unscaled, so that neither a branch nor the multiply pulls the load -- and a wait for it and for every atomic in
+            // flight -- down to the end of the iteration, where the compiler put the parent's `if (l + 1 < len)` form
+            const float k_next = kp[(long)min(l + 1, len - 1) * ks];
+            send_prev(l);
+            // this key's de row and row sum (same address in every lane: broadcast), issued with them, ahead of the arithmetic
+            f32x4 dc[8];
+#pragma unroll
+            for (int i4 = 0; i4 < 8; ++i4) dc[i4] = *reinterpret_cast<const f32x4*>(de_s + l * 32 + i4 * 4);
+            const float dsc = ds_s[l];
+            __builtin_amdgcn_sched_barrier(0);
             const float ek = __builtin_amdgcn_exp2f(kv);
             const f32x2 ek2 = {ek, ek};
-            f32x2 dk2 = {0.f, 0.f}, dr2 = {0.f, 0.f}, ds2 = {0.f, 0.f};
+            f32x2 dk2 = {0.f, 0.f}, dr2 = {0.f, 0.f};
 #pragma unroll
             for (int i4 = 0; i4 < 8; ++i4) {
-                const float4 d4 = *reinterpret_cast<const float4*>(de_s + l * 32 + i4 * 4);     // same address in every lane: broadcast
-                const f32x2 d01 = {d4.x, d4.y}, d23 = {d4.z, d4.w};
-                ds2 = ds2 + d01 + d23;
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int i = i4 * 2 + h;
-                    const f32x2 d = h ? d23 : d01;
+                    const f32x2 d = h ? dc[i4].zw : dc[i4].xy;
                     const f32x2 den = pk_fma(eq2[i], ek2, one);
                     const f32x2 r = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
                     const f32x2 u = pk_fma(-r, r, r);            // r (1 - r) = (1 - tanh^2) / 4
@@ -391,9 +457,16 @@ __global__ __launch_bounds__(256) void attn_dqdk_k(const float* __restrict__ Q, 
                     dr2 = pk_fma(d, r, dr2);
                 }
             }
-            dkp = dk2.x + dk2.y;
-            dva += (ds2.x + ds2.y) - 2.f * (dr2.x + dr2.y);
-        } else {
+            dva += dsc - 2.f * (dr2.x + dr2.y);
+            dk_prev = (dk2.x + dk2.y) * va4;
+            kv = C2 * k_next;
+            if (++l >= len) break;
+        }
+        if (l >= len) break;
+        {                               // one sum-form key
+            const float k_next = kp[(long)min(l + 1, len - 1) * ks];
+            send_prev(l);
+            float dkp = 0.f;
 #pragma unroll
             for (int i4 = 0; i4 < 8; ++i4) {
                 const float4 d4 = *reinterpret_cast<const float4*>(de_s + l * 32 + i4 * 4);
@@ -409,9 +482,12 @@ __global__ __launch_bounds__(256) void attn_dqdk_k(const float* __restrict__ Q, 
                     dva = fmaf(d[j], fmaf(-2.f, r, 1.f), dva);
                 }
             }
+            dk_prev = dkp * va4;
+            kv = C2 * k_next;
+            ++l;
         }
-        if (av) atomicAdd(dK + ((long)l * B + b) * A + a, dkp * va4);
     }
+    send_prev(len);
     if (av) {
 #pragma unroll
         for (int i = 0; i < 32; ++i) {
@@ -460,7 +536,7 @@ extern "C" int ft_attention_bwd(const float* Q, const float* K, const float* v, 
     FT_CHECK_ARG(T >= 1 && B >= 1 && L >= 1 && A >= 1 && temperature > 0.f);
     FT_CHECK_ARG(prior == nullptr || p_save != nullptr);
     FT_CHECK_ARG(B <= 65535);
-    const size_t lds_q = sizeof(float) * ((size_t)L * 32);
+    const size_t lds_q = sizeof(float) * ((size_t)L * 33);       // the de tile and its row sums
     if (lds_q > (size_t)MAX_LDS - 1024)
         return ft_fail(FT_EUNSUPPORTED, "ft_attention_bwd: L=%d exceeds the LDS tile (%zu B)", L, lds_q);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

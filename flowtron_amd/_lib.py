@@ -85,6 +85,7 @@ class DecodeBatchArgs(C.Structure):
 
 SUMSQ_PARTIALS = 1024      # FT_SUMSQ_PARTIALS: floats of scratch ft_sumsq needs
 RESAMPLE_MAX_PHASES, RESAMPLE_MAX_TAPS = 2048, 20480     # FT_RESAMPLE_MAX_*: the tap table ft_resample_ragged holds in LDS
+STYLE_BATCH, STYLE_TIME_AND_BATCH = 0, 1                 # FT_STYLE_*: what ft_style_accumulate sums
 
 # name -> argtypes (every symbol include/flowtron_hip.h declares; checked by tests/test_host_cpu.py)
 SIGNATURES = {
@@ -192,6 +193,8 @@ SIGNATURES = {
     "ft_istft_pow2_ragged": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "ft_resample_ragged": ([_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p], _i),
     "ft_resample_out_len": ([_l, _i, _i], _l),
+    "ft_style_accumulate": ([_p, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p], _i),
+    "ft_style_sample": ([_p, _p, _p, _i, _i, _i, _i, _d, _d, _i, _p], _i),
     "ft_attn_ctc_workspace_floats":([_i, _i, _i], _sz),
     "ft_attn_ctc_fwd": ([_p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _p], _i),
     "ft_attn_ctc_bwd": ([_p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _p], _i),

@@ -716,6 +716,42 @@ class Flowtron(nn.Module):
                 x, log_s_list, gate, attns_list, attns_logprob_list = run_flows(x0, enc)
         return x, log_s_list, gate, attns_list, attns_logprob_list, None, None, None
 
+    def latents(self, mel, speaker_ids, text, in_lens, out_lens, attn_prior=None):
+        """z of a batch of utterances for style transfer (inference_style_transfer.ipynb runs `model(...)[0]` utterance by utterance):
+        one no-grad batched forward -> z [B, M, T], zeros behind out_lens[b].  mel [B,M,T], speaker_ids [B], text [B,L], attn_prior
+        [B,T,L] | None; in_lens / out_lens as for infer (lists, CPU or device integer tensors, 1 ..= L and 1 ..= T).  The utterances
+        may come in any order: the forward sees them sorted by text length, descending, as the reference's collate function hands
+        them over, and z comes back in the caller's order.  eval() mode only: the encoder's dropout would make z random."""
+        if self.training:
+            raise ValueError("latents needs model.eval(): in training mode the encoder's dropout makes z random")
+        L.require_cuda(mel, speaker_ids, text, attn_prior)
+        if mel.dim() != 3 or text.dim() != 2 or text.shape[0] != mel.shape[0]:
+            raise ValueError("mel must be [B, M, T] and text [B, L] with the same B, got %s and %s"
+                             % (tuple(mel.shape), tuple(text.shape)))
+        B, T = mel.shape[0], mel.shape[2]
+        il = lengths_arg(in_lens, "in_lens", B, text.shape[1])
+        ol = lengths_arg(out_lens, "out_lens", B, T)
+        if il is None or ol is None:
+            raise ValueError("in_lens and out_lens must be given")
+        dev = mel.device
+        order = sorted(range(B), key=lambda b: -il[b])            # stable: equal lengths keep the caller's order
+        if order != list(range(B)):
+            idx = torch.tensor(order, dtype=torch.long, device=dev)
+            mel, speaker_ids, text = mel.index_select(0, idx), speaker_ids.index_select(0, idx), text.index_select(0, idx)
+            if attn_prior is not None:
+                attn_prior = attn_prior.index_select(0, idx)
+        with torch.no_grad():
+            x = self(mel, speaker_ids, text, torch.tensor([il[b] for b in order], dtype=torch.long, device=dev),
+                     torch.tensor([ol[b] for b in order], dtype=torch.long, device=dev), attn_prior)[0]       # [T,B,M]
+            z = x.permute(1, 2, 0)
+            if order != list(range(B)):
+                inv = [0] * B
+                for pos, b in enumerate(order):
+                    inv[b] = pos
+                z = z.index_select(0, torch.tensor(inv, dtype=torch.long, device=dev))
+            pad = torch.arange(T, device=dev)[None, :] >= torch.tensor(ol, device=dev)[:, None]               # [B,T]
+            return z.masked_fill(pad[:, None, :], 0.0)
+
     def infer(self, residual, speaker_ids, text, temperature=1.0, gate_threshold=0.5, attns=None, attn_prior=None,
               in_lens=None, out_lens=None, return_lengths=False):
         """residual [B,M,N], speaker_ids [B] or [B,1], text [B,L] -> (mel [B,M,N'], attention_weights: per flow a list of N' rows

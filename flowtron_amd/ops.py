@@ -2374,3 +2374,25 @@ class LSTM2SeqFn(torch.autograd.Function):
 def lstm2_supported(B, H, mode):
     import os
     return (L.is16(mode) and os.environ.get("FLOWTRON_LSTM2", "1") != "0" and bool(L.lib().ft_lstm2_supported(B, H)))
+
+
+# --------------------------------------------------------------------------
+# style transfer: posterior over z from reference utterances (inference_style_transfer.ipynb; csrc/style.hip)
+# --------------------------------------------------------------------------
+def style_accumulate(z, lens32_, acc, n_frames, mode):
+    """acc (float64, [M, n_frames] or [M]) += the B utterances of z [B,M,T] fp32 of ANY strides (read in place), in order of b."""
+    L.require_cuda(z, lens32_, acc)
+    B, M, T = z.shape
+    sb, sm, st = z.stride()
+    L.check(L.lib().ft_style_accumulate(L.ptr(z), sb, sm, st, L.ptr(lens32_), L.ptr(acc), B, M, T, n_frames, mode, L.stream()),
+            "ft_style_accumulate")
+
+
+def style_sample(acc, count, lambd, M, n_frames, mode, eps=None, sigma=0.0):
+    """-> fp32 [S, M, n_frames] = mu + sigma * eps (eps [S,M,n_frames] fp32 contiguous), or mu itself [1, M, n_frames] without eps."""
+    L.require_cuda(acc, eps)
+    S = 1 if eps is None else eps.shape[0]
+    out = torch.empty(S, M, n_frames, device=acc.device, dtype=torch.float32)
+    L.check(L.lib().ft_style_sample(L.ptr(acc), L.ptr(eps), L.ptr(out), S, M, n_frames, count, float(lambd), float(sigma), mode,
+                                    L.stream()), "ft_style_sample")
+    return out

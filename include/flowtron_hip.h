@@ -623,6 +623,28 @@ int ft_resample_ragged(const float* x, const int32_t* n_samples, const float* ta
 /* host arithmetic only: ceil(n new / orig) in 64 bits; -1 for n < 0 or a rate < 1 */
 int64_t ft_resample_out_len(int64_t n, int orig, int new_rate);
 
+/* ---- style transfer: posterior over z from reference utterances (inference_style_transfer.ipynb; csrc/style.hip) -------
+ * The notebook's posterior mean of z given K reference latents z_b [M][len_b] under the prior N(0, 1):
+ *   ratio = K / lambd,   mu = ratio / (ratio + 1) * acc / K,   acc summed over the utterances b:
+ *   FT_STYLE_BATCH           acc [M][n_frames]:  acc[m][t] += z_b[m][t mod len_b]   (every utterance tiled along time)
+ *   FT_STYLE_TIME_AND_BATCH  acc [M]:            acc[m] += (sum_{t < len_b} z_b[m][t]) / len_b   (n_frames is not used: pass 1)
+ * accumulate: adds the B utterances of one batch, in order of b, into the float64 accumulator `acc`, which the caller owns
+ * and zeroes once per reference set.  z is fp32 with ELEMENT strides (utterance, mel, frame), so the forward's time-major
+ * [T][B][M] output and a [B][M][T] tensor are both read in place; lens [B] device int32, clamped to 1 ..= T inside the
+ * kernel; frames at or behind lens[b] are never read.  One launch, no floating-point atomics: each element of acc belongs
+ * to one thread, a time sum is 16 strided partial sums (t = j, j + 16, ..., ascending) folded by one fixed tree.  A reference
+ * set therefore gives the same bits however it is split into calls and whatever T its batches are padded to.
+ * sample: out [S][M][n_frames] fp32 = mu + sigma * eps[s][m][t] (TIME_AND_BATCH: mu[m] at every t), formed in float64 and
+ * rounded to fp32 once; eps fp32 [S][M][n_frames] standard normal draws of the caller's, or NULL with S = 1: out = mu.
+ * K = the utterances accumulated so far.  One launch.
+ * FT_EINVAL before any device call: a NULL pointer (but eps), B, M, T, n_frames, S or K < 1, lambd <= 0, a negative stride,
+ * an unknown mode, eps == NULL with S != 1, acc not 8-byte aligned, M > 16 * 65535 (the accumulate grid). */
+enum { FT_STYLE_BATCH = 0, FT_STYLE_TIME_AND_BATCH = 1 };
+int ft_style_accumulate(const float* z, int64_t stride_b, int64_t stride_m, int64_t stride_t, const int32_t* lens, double* acc,
+                        int B, int M, int T, int n_frames, int mode, void* stream);
+int ft_style_sample(const double* acc, const float* eps, float* out, int S, int M, int n_frames, int K, double lambd,
+                    double sigma, int mode, void* stream);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

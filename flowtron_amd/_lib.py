@@ -195,6 +195,9 @@ SIGNATURES = {
     "ft_resample_out_len": ([_l, _i, _i], _l),
     "ft_style_accumulate": ([_p, _l, _l, _l, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "ft_style_sample": ([_p, _p, _p, _i, _i, _i, _i, _d, _d, _i, _p], _i),
+    "ft_mas_workspace_bytes": ([_i, _i, _i], _sz),
+    "ft_mas_ragged": ([_p, _l, _l, _l, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i, _p], _i),
+    "ft_durations_to_rows": ([_p, _p, _p, _i, _i, _i, _i, _p], _i),
     "ft_attn_ctc_workspace_floats":([_i, _i, _i], _sz),
     "ft_attn_ctc_fwd": ([_p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _p], _i),
     "ft_attn_ctc_bwd": ([_p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _p], _i),

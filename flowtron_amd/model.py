@@ -722,8 +722,19 @@ class Flowtron(nn.Module):
         [B,T,L] | None; in_lens / out_lens as for infer (lists, CPU or device integer tensors, 1 ..= L and 1 ..= T).  The utterances
         may come in any order: the forward sees them sorted by text length, descending, as the reference's collate function hands
         them over, and z comes back in the caller's order.  eval() mode only: the encoder's dropout would make z random."""
+        out, unsort, _, ol = self._forward_any_order("latents", mel, speaker_ids, text, in_lens, out_lens, attn_prior)
+        with torch.no_grad():
+            dev, T = mel.device, mel.shape[2]
+            z = unsort(out[0].permute(1, 2, 0))                                                                # [T,B,M] -> [B,M,T]
+            pad = torch.arange(T, device=dev)[None, :] >= torch.tensor(ol, device=dev)[:, None]               # [B,T]
+            return z.masked_fill(pad[:, None, :], 0.0)
+
+    def _forward_any_order(self, what, mel, speaker_ids, text, in_lens, out_lens, attn_prior):
+        """The no-grad batched forward behind latents() and alignments(): the utterances in any order, the forward sees them
+        sorted by text length, descending.  -> (the forward's tuple in SORTED order, unsort: a function that puts a tensor
+        whose first dimension is the batch back into the caller's order, in_lens and out_lens as lists in the caller's order)."""
         if self.training:
-            raise ValueError("latents needs model.eval(): in training mode the encoder's dropout makes z random")
+            raise ValueError("%s needs model.eval(): in training mode the encoder's dropout makes z random" % what)
         L.require_cuda(mel, speaker_ids, text, attn_prior)
         if mel.dim() != 3 or text.dim() != 2 or text.shape[0] != mel.shape[0]:
             raise ValueError("mel must be [B, M, T] and text [B, L] with the same B, got %s and %s"
@@ -741,16 +752,76 @@ class Flowtron(nn.Module):
             if attn_prior is not None:
                 attn_prior = attn_prior.index_select(0, idx)
         with torch.no_grad():
-            x = self(mel, speaker_ids, text, torch.tensor([il[b] for b in order], dtype=torch.long, device=dev),
-                     torch.tensor([ol[b] for b in order], dtype=torch.long, device=dev), attn_prior)[0]       # [T,B,M]
-            z = x.permute(1, 2, 0)
+            out = self(mel, speaker_ids, text, torch.tensor([il[b] for b in order], dtype=torch.long, device=dev),
+                       torch.tensor([ol[b] for b in order], dtype=torch.long, device=dev), attn_prior)
+            inv_idx = None
             if order != list(range(B)):
                 inv = [0] * B
                 for pos, b in enumerate(order):
                     inv[b] = pos
-                z = z.index_select(0, torch.tensor(inv, dtype=torch.long, device=dev))
-            pad = torch.arange(T, device=dev)[None, :] >= torch.tensor(ol, device=dev)[:, None]               # [B,T]
-            return z.masked_fill(pad[:, None, :], 0.0)
+                inv_idx = torch.tensor(inv, dtype=torch.long, device=dev)
+        return out, (lambda t: t if inv_idx is None else t.index_select(0, inv_idx)), il, ol
+
+    def alignments(self, mel, speaker_ids, text, in_lens, out_lens, attn_prior=None):
+        """The attention of every flow over a batch of utterances, ready for flowtron_amd.align: the same no-grad batched forward
+        as latents() -> (z [B, M, T], attn [F, B, T, L], attn_logprob [F, B, T, L]).  Arguments as for latents(): any order of
+        the utterances, results in the caller's order, eval() mode only.  EVERY flow is in natural time: the maps of the odd
+        flows, which the forward hands back in reversed time, are reversed by length on the device (ops.reverse_by_length).
+        Zeros lie behind out_lens[b] and behind in_lens[b]."""
+        out, unsort, il, ol = self._forward_any_order("alignments", mel, speaker_ids, text, in_lens, out_lens, attn_prior)
+        with torch.no_grad():
+            dev, T, Lt = mel.device, mel.shape[2], text.shape[1]
+            ol_t, il_t = torch.tensor(ol, device=dev), torch.tensor(il, device=dev)
+            pad_t = torch.arange(T, device=dev)[None, :] >= ol_t[:, None]                                      # [B,T]
+            pad = pad_t[:, :, None] | (torch.arange(Lt, device=dev)[None, :] >= il_t[:, None])[:, None, :]     # [B,T,L]
+            out32 = ol_t.to(torch.int32)
+            maps = []
+            for per_flow in (out[3], out[4]):
+                flows = []
+                for f, a in enumerate(per_flow):
+                    a = unsort(a.detach())
+                    if f % 2 == 1:
+                        a = ops.reverse_by_length(a, out32, False)
+                    flows.append(a.masked_fill(pad, 0.0))
+                maps.append(torch.stack(flows))
+            z = unsort(out[0].permute(1, 2, 0)).masked_fill(pad_t[:, None, :], 0.0)
+            return z, maps[0], maps[1]
+
+    def infer_aligned(self, residual, speaker_ids, text, alignment, in_lens=None, n_frames=None, temperature=1.0,
+                      gate_threshold=1.0):
+        """Decodes a batch along GIVEN alignments (durations from flowtron_amd.align, or the soft maps of alignments()):
+        residual [B, M, N], text [B, L], alignment [B, N, L] (used by every flow) or [F, B, N, L] (one per flow), hard or soft,
+        ALWAYS in natural time -- the rows of an odd flow are flipped here, over the utterance's own frames.  in_lens [B]: text
+        positions per utterance (None = L); n_frames [B]: frames per utterance (None = N); lists or integer tensors.
+        Utterance b is decoded exactly as infer(residual[b:b+1, :, :n_b], speaker_ids[b:b+1], text[b:b+1, :L_b], attns=[its rows
+        per flow, in the flow's own time order], gate_threshold=...) decodes it: a loop over the staged forced-decode chain.
+        gate_threshold 1.0 (the default) lets the alignment decide the length; a lower one lets the gate cut it.
+        -> (mel [B, M, N'] with zeros behind each utterance's frames, lengths: CPU int64 [B])."""
+        L.require_cuda(residual, text, alignment)
+        if residual.dim() != 3 or text.dim() != 2 or text.shape[0] != residual.shape[0]:
+            raise ValueError("residual must be [B, M, N] and text [B, L] with the same B, got %s and %s"
+                             % (tuple(residual.shape), tuple(text.shape)))
+        B, N, Lt, F_ = residual.shape[0], residual.shape[2], text.shape[1], len(self.flows)
+        if not torch.is_tensor(alignment) or tuple(alignment.shape) not in ((B, N, Lt), (F_, B, N, Lt)):
+            raise ValueError("alignment must be [B, N, L] = %s or [F, B, N, L] = %s, got %s"
+                             % ((B, N, Lt), (F_, B, N, Lt), tuple(alignment.shape) if torch.is_tensor(alignment) else type(alignment).__name__))
+        il = lengths_arg(in_lens, "in_lens", B, Lt) or [Lt] * B
+        nf = lengths_arg(n_frames, "n_frames", B, N) or [N] * B
+        sid = speaker_ids.reshape(B, -1)
+        outs = []
+        for b in range(B):
+            rows = []
+            for f in range(F_):
+                a = (alignment[f, b] if alignment.dim() == 4 else alignment[b])[:nf[b], :il[b]].float()
+                rows.append(torch.flip(a, (0,)) if f % 2 == 1 else a)
+            m, _ = self.infer(residual[b:b + 1, :, :nf[b]], sid[b:b + 1], text[b:b + 1, :il[b]], temperature=temperature,
+                              gate_threshold=gate_threshold, attns=rows)
+            outs.append(m)
+        n = [int(m.shape[2]) for m in outs]
+        mel = residual.new_zeros(B, outs[0].shape[1], max(n), dtype=torch.float32)
+        for b, m in enumerate(outs):
+            mel[b, :, :n[b]] = m[0]
+        return mel, torch.tensor(n, dtype=torch.int64)
 
     def infer(self, residual, speaker_ids, text, temperature=1.0, gate_threshold=0.5, attns=None, attn_prior=None,
               in_lens=None, out_lens=None, return_lengths=False):

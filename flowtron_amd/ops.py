@@ -2396,3 +2396,34 @@ def style_sample(acc, count, lambd, M, n_frames, mode, eps=None, sigma=0.0):
     L.check(L.lib().ft_style_sample(L.ptr(acc), L.ptr(eps), L.ptr(out), S, M, n_frames, count, float(lambd), float(sigma), mode,
                                     L.stream()), "ft_style_sample")
     return out
+
+
+# --------------------------------------------------------------------------
+# token durations and alignments from durations (csrc/align.hip)
+# --------------------------------------------------------------------------
+def mas_ragged(logp, in32, out32, want_score=False):
+    """Monotonic alignment search of a ragged batch: logp [B,T,L] fp32 of ANY strides (read in place), device int32 lengths ->
+    (path [B,T] int32, durations [B,L] int32, score [B] fp32 | None)."""
+    L.require_cuda(logp, in32, out32)
+    B, T, Lt = logp.shape
+    dev = logp.device
+    path = torch.empty(B, T, device=dev, dtype=torch.int32)
+    dur = torch.empty(B, Lt, device=dev, dtype=torch.int32)
+    score = torch.empty(B, device=dev, dtype=torch.float32) if want_score else None
+    nbytes = L.lib().ft_mas_workspace_bytes(B, T, Lt)
+    work = torch.empty(nbytes // 8, device=dev, dtype=torch.int64)
+    sb, st, sl = logp.stride()
+    L.check(L.lib().ft_mas_ragged(L.ptr(logp), sb, st, sl, L.ptr(in32), L.ptr(out32), L.ptr(path), L.ptr(dur), L.ptr(score),
+                                  L.ptr(work), nbytes, B, T, Lt, L.stream()), "ft_mas_ragged")
+    return path, dur, score
+
+
+def durations_to_rows(dur32, in32, n_frames, reverse=False):
+    """durations [B,L] int32 contiguous -> one-hot alignment rows [B, n_frames, L] fp32 (reverse: each utterance's own frames in
+    reversed time), zeros behind an utterance's total and its tokens."""
+    L.require_cuda(dur32, in32)
+    B, Lt = dur32.shape
+    rows = torch.empty(B, n_frames, Lt, device=dur32.device, dtype=torch.float32)
+    L.check(L.lib().ft_durations_to_rows(L.ptr(dur32), L.ptr(in32), L.ptr(rows), B, n_frames, Lt, int(bool(reverse)), L.stream()),
+            "ft_durations_to_rows")
+    return rows

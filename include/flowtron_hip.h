@@ -645,6 +645,34 @@ int ft_style_accumulate(const float* z, int64_t stride_b, int64_t stride_m, int6
 int ft_style_sample(const double* acc, const float* eps, float* out, int S, int M, int n_frames, int K, double lambd,
                     double sigma, int mode, void* stream);
 
+/* ---- token durations and alignments from durations (csrc/align.hip; additive, not in the reference) -------------------
+ * mas_ragged: monotonic alignment search over a ragged batch, one launch, one workgroup per utterance.  logp: fp32 scores
+ * with ELEMENT strides (utterance, frame, token), so a slice of the forward's attn_logprob [B][T][L] or of a stacked
+ * [F][B][T][L] tensor is read in place; in_lens / out_lens [B] device int32, clamped inside the kernel to 1 ..= L and 1 ..= T;
+ * only scores with t < T_b = out_lens[b] and l < L_b = in_lens[b] are read.  Per utterance
+ *     Q[0][0] = s[0][0];   Q[t][l] = s[t][l] + (adv[t][l] ? Q[t-1][l-1] : Q[t-1][l])   for l <= min(t, L_b - 1)
+ *     adv[t][l] = l > 0 && (l == t || Q[t-1][l-1] > Q[t-1][l])     (strict: a tie stays)
+ *     backtrack from (T_b - 1, L_b - 1):  path[t] = l;  l -= adv[t][l]
+ * one fp32 add and one compare per cell, so a float32 replay on the host gives the same bits.  Among the best-scoring
+ * monotone paths this is the one that advances earliest, and it is structurally valid whatever the scores (all -inf too):
+ * path[0] = 0, path[T_b-1] = L_b - 1, steps of 0 or 1.
+ * path [B][T] int32, -1 behind T_b; durations [B][L] int32: frames per token, each >= 1, sum T_b, 0 behind L_b; score [B] fp32
+ * = Q[T_b-1][L_b-1], or NULL.  An utterance with L_b > T_b has no monotone path: path -1, durations 0, score -inf.
+ * work: the backpointers, one bit per cell, mas_workspace_bytes bytes (host arithmetic only; 0 for a size < 1), 8-byte
+ * aligned; contents need not be initialised.  No atomics, no communication between workgroups.
+ * durations_to_rows: rows [B][N][L] fp32, rows[b][n][l] = 1 where cum[l-1] <= n < cum[l] and l < in_lens[b], with cum the
+ * running sum of max(durations[b][l], 0); every other element 0, rows at or behind the utterance's total included.
+ * reverse != 0: utterance b's rows in reversed time (row n holds frame total_b - 1 - n), the order an odd flow decodes in.
+ * One launch; the scan over L runs inside each workgroup.
+ * FT_EINVAL before any device call: a NULL pointer (but score), B, T, L or N < 1, a negative stride, work misaligned or
+ * work_bytes too small.  FT_EUNSUPPORTED: mas_ragged with L > 1024 (the text limit of the batched decode). */
+size_t ft_mas_workspace_bytes(int B, int T, int L);
+int ft_mas_ragged(const float* logp, int64_t stride_b, int64_t stride_t, int64_t stride_l, const int32_t* in_lens,
+                  const int32_t* out_lens, int32_t* path, int32_t* durations, float* score, void* work, size_t work_bytes,
+                  int B, int T, int L, void* stream);
+int ft_durations_to_rows(const int32_t* durations, const int32_t* in_lens, float* rows, int B, int N, int L, int reverse,
+                         void* stream);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

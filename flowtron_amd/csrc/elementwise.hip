@@ -259,11 +259,12 @@ __global__ void nll_sums_k(const float* __restrict__ z, LsPtrs ls, int n_ls, lon
     if (threadIdx.x == 0) { atomicAdd(acc, s2); atomicAdd(acc + 1, sl); }
 }
 
-__global__ void loss_finalize_k(float* __restrict__ acc, const int* __restrict__ lens, int B, int M, float two_sigma2,
+// n counts the frames the sums above visited: t < lens[b] over t < T, so a length beyond T (or below 0) is clamped here as it is there
+__global__ void loss_finalize_k(float* __restrict__ acc, const int* __restrict__ lens, int T, int B, int M, float two_sigma2,
                                 float* __restrict__ nll_out, float* __restrict__ gate_out) {
     __shared__ float red[NT / 64];
     float n = 0.f;
-    for (int b = threadIdx.x; b < B; b += blockDim.x) n += (float)lens[b];
+    for (int b = threadIdx.x; b < B; b += blockDim.x) { const int l = lens[b]; n += (float)(l < 0 ? 0 : (l > T ? T : l)); }
     n = block_sum(n, red);
     if (threadIdx.x == 0) {
         const float nm = n * (float)M;
@@ -647,7 +648,7 @@ extern "C" int ft_flowtron_loss_fwd(const float* z, const float* const* log_s, i
     if (gate)
         hipLaunchKernelGGL(gate_bce_fwd_k, dim3(grid_for((int64_t)T * B, NT, 256)), dim3(NT), 0, ST(stream), gate, gate_target, out_lens, acc + 2,
                            T, B);
-    hipLaunchKernelGGL(loss_finalize_k, dim3(1), dim3(NT), 0, ST(stream), acc, out_lens, B, M, 2.0f * sigma * sigma, nll_out, gate_out);
+    hipLaunchKernelGGL(loss_finalize_k, dim3(1), dim3(NT), 0, ST(stream), acc, out_lens, T, B, M, 2.0f * sigma * sigma, nll_out, gate_out);
     FT_CHECK_LAUNCH();
     return FT_OK;
 }

@@ -267,7 +267,9 @@ int ft_col2im(const float* dcol, float* dx, const int32_t* lens, int L, int B, i
 /* ---- masked instance norm + ReLU (+dropout keep-mask) (flowtron.py:53-92, :502)
  * x,y [L,B,C]; statistics over l < lens[b] (biased variance, eps); y = relu(xhat*gamma+beta)*keep,
  * y = 0 at l >= lens[b].  keep may be NULL.  Saves mean/rstd [B,C] for backward.
- * bwd: dx (0 at pads), dgamma/dbeta [C] (overwritten). */
+ * bwd: dx (0 at pads), dgamma/dbeta [C] (overwritten).
+ * lens[b] beyond L counts as L.  A sample with lens[b] <= 0 has y = 0 and dx = 0 everywhere and adds nothing to dgamma / dbeta; its
+ * mean / rstd entries are not defined (0 / 0) and bwd, their only reader, does not use them. */
 int ft_instnorm_relu_fwd(const float* x, const float* gamma, const float* beta, const float* keep,
                          const int32_t* lens, float* y, float* mean, float* rstd,
                          int L, int B, int C, float eps, void* stream);
@@ -448,7 +450,8 @@ int ft_gate_bce_bwd(const float* gate, const float* target, const int32_t* lens,
  * The per-term entry points above leave the scalar arithmetic (frame count, normalisers, g / n) to the caller -- ~40 four-byte
  * kernels per training step right where train.py:300-303 waits for the losses.  fwd: acc (8 floats, zeroed here) receives
  * [0] sum_valid z^2, [1] sum_f sum_valid log_s[f], [2] sum_valid BCE, and from a one-workgroup kernel [4] 1 / (n M), [5] 1 / n,
- * [6] n = sum(out_lens); nll_out[0] = (acc[0] / (2 sigma^2) - acc[1]) / (n M), gate_out[0] = acc[2] / n (gate, gate_target,
+ * [6] n = sum_b min(max(out_lens[b], 0), T) -- the frames the masked sums visit (they mask with t < out_lens[b] over t < T, so a length
+ * beyond T counts as T in n as well); nll_out[0] = (acc[0] / (2 sigma^2) - acc[1]) / (n M), gate_out[0] = acc[2] / n (gate, gate_target,
  * gate_out all NULL: no gate term).  z [T,B,M] contiguous; log_s = HOST array of n_ls (<= 8) device pointers to [T,B,M] views
  * with row stride ld_ls; gate [T,B], gate_target [B,T].
  * bwd (reads acc as fwd left it; g_nll / g_gate = device scalars, the gradients of the two outputs): dz = g_nll z / (sigma^2 n M),

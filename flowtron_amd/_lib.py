@@ -133,6 +133,7 @@ SIGNATURES = {
     "ft_lstm_persist_bwd": ([_p, _l, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
     "ft_bilstm_persist_supported": ([_i, _i], _i),
     "ft_bilstm_persist_workspace_bytes": ([_i, _i], C.c_size_t),
+    "ft_bilstm_persist_debug_prof": ([_p], _i),
     "ft_bilstm_persist_fwd": ([_p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p], _i),
     "ft_bilstm_persist_bwd": ([_p, _l, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p], _i),
     "ft_lstm_persist_bwd_img": ([_p, _l, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _l, _l, _p, _p], _i),

@@ -2,14 +2,16 @@
 // ONE launch per pass for both directions and all time steps, instead of one launch per step (lstm.hip lstm_*_pair, 4.4 / 4.9 us
 // per step at the launch floor).
 //
-// H = 256 is small enough for a much simpler organisation than lstm_persist.hip: there is NO workgroup-level step at all.
+// H = 256 is small enough for a much simpler organisation than lstm_persist.hip.
 //   group      = (XCD x, direction d): batch rows [4x, 4x + 4) of that direction, for the whole sequence; formed at run time from
-//                the workgroups' XCC ids (census, as in lstm_persist.hip), hand-off through that XCD's own L2;
+//                the workgroups' XCC ids (census, as in lstm_persist.hip), hand-off through that XCD's own L2; 16 workgroups per
+//                group in both passes, so all 32 CUs of an XCD work;
 //   forward    every WAVE is an independent agent that owns 4 hidden units (one 16-column MFMA tile = 4 units x 4 gates) with
 //                the whole K = 256: 8 MFMAs per step, no K split, hence no LDS reduction and no barrier -- the four gates of a
-//                unit are gathered into one lane with three DPP row shifts.  64 waves = 16 workgroups per group;
-//   backward   a wave owns 16 hidden units (one column tile of W_hh^T, K = 4H = 1024: 32 MFMAs per step); 16 waves = 4 workgroups
-//                per group;
+//                unit are gathered into one lane with three DPP row shifts.  64 waves per group;
+//   backward   a WORKGROUP owns 16 hidden units (one column tile of W_hh^T, K = 4H = 1024) and splits K over its four waves: wave g
+//                polls and multiplies the dgates of gate g (a quarter of the hand-off bytes, 8 of the 32 MFMAs), the partials are
+//                summed through LDS in a fixed order behind one barrier per step (see bilstm_bwd_body);
 //   hand-off   h_t / dgates_s as 8-byte {epoch, 16-bit pair} granules in the packed layout of lstm_persist.hip (one 16-byte load
 //                per lane fetches four k-chunks of the group's four rows; DPP row shifts move them into the MFMA row positions),
 //                plain stores, nt loads, two parity buffers, bounded spins with a status word;
@@ -70,7 +72,7 @@ struct BiBwdP {
     const float* dy; long ldy; const int* lens; const float* gates[2]; const float* cell[2]; float* dgx[2];
     const unsigned short* wTfrag[2];     // make_wfrag_bwd images
     unsigned long long* gran;            // [2 parity][8 xcd][2 dir][GRAN_B]
-    int* status; unsigned* census; int T, B; long timeout_ticks;
+    int* status; unsigned* census; int T, B; long timeout_ticks; long* prof;
 };
 
 // XCD census: group = this workgroup's XCC id, slot = arrival order inside that XCD (lstm_persist.hip)
@@ -92,13 +94,14 @@ __device__ __forceinline__ bool join(unsigned* census, int* status, int tid, int
     return true;
 }
 
-// poll NL load groups (two 16-byte loads each) of this group's vector until every tag shows `epoch`; false = timed out
+// poll NL load groups (two 16-byte loads each) of this group's vector, from the wave-uniform byte offset `soff` on, until every tag
+// shows `epoch`; false = timed out
 template <int NL>
 __device__ __forceinline__ bool poll(u32x4 (&ld)[NL][2], __amdgpu_buffer_rsrc_t rs, int voff, unsigned epoch, long t_start,
-                                     long timeout_ticks, int* status) {
+                                     long timeout_ticks, int* status, int soff = 0) {
     auto issue = [&](int g) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) ld[g][h] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, (g * 2 + h) * 1024, 2);   // nt
+        for (int h = 0; h < 2; ++h) ld[g][h] = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff + (g * 2 + h) * 1024, 2);   // nt
     };
 #pragma unroll
     for (int g = 0; g < NL; ++g) issue(g);
@@ -205,16 +208,36 @@ __global__ __launch_bounds__(256) void bilstm_persist_fwd_k(BiFwdP p) {
     if (dead && lane == 0) atomicExch(p.status, 1);
 }
 
-__global__ __launch_bounds__(256) void bilstm_persist_bwd_k(BiBwdP p) {
-    extern __shared__ float occupancy_pad[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// Backward step, K split inside the workgroup.  A workgroup owns one column tile of W_hh^T (16 hidden units) of its group, its four
+// waves the four k-quarters of the sum over k = gate * 256 + unit -- wave g polls and multiplies the dgates of gate g only: two load
+// groups (4 KB of granules), 8 weight fragments, 8 MFMAs in two independent chains.  The four 4 x 16 fp32 partials meet in LDS
+// (`part`, two parity buffers) behind ONE barrier per step and are summed in the fixed order 0, 1, 2, 3 by wave 0, which finishes
+// the 64 (row, unit) elements: row loads, cell backward, four granule and four dgx stores per lane.  Waves 1..3 carry nothing but
+// their poll in the vector-memory queue.  (All four waves finishing redundantly and each publishing one gate -- one store of each
+// kind per lane behind the next poll -- measured 5 us per launch SLOWER at T 157: profiles/bilstm_bwd_split_variants.log.)
+//
+// Parity buffers and the one barrier: a wave writes part[s & 1] again at step s + 2, which it reaches only through the barrier of step
+// s + 1; wave 0 arrives there after its reads of step s have returned (they feed the cell backward in front of it).
+//
+// Leaving: a wave whose poll gives up (time-out, or another workgroup's status) does NOT leave on its own.  It raises quit[s & 1]
+// and arrives at the step's barrier like everybody else, and the other waves read that flag BEHIND the barrier: the decision is
+// the same for the whole workgroup, nobody is left waiting at a barrier.  The flag has the partials' parity for the partials'
+// reason: a wave that is already in step s + 1 raises quit[(s + 1) & 1], which a slower wave still reading the flag of step s does
+// not look at, and it cannot reach step s + 2 before that wave has read.  A raised flag is never lowered.
+// PROF: stage stamps (100 MHz wall clock) of workgroup (XCD 0, slot 0): prof[(s * 4 + wave) * 6 + {top, polled, partial written,
+// reduced, cell done, published}], s < 1024; waves 1..3 stamp the first four.
+template <bool PROF>
+__device__ __forceinline__ void bilstm_bwd_body(const BiBwdP& p) {
+    __shared__ f32x4 part[2][4][16];                     // [parity][k-quarter][unit]: rows 0..3 of the quarter's partial of dh_rec
+    __shared__ int quit[2];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kg = lane >> 4;
+    if (tid < 2) quit[tid] = 0;                          // (join's barrier stands between this and the first read)
     int xcd, q;
     if (!join(p.census, p.status, tid, xcd, q)) return;
-    if (q >= 8) return;                                  // 4 workgroups per (XCD, direction)
-    const int dir = q >> 2, m = q & 3;
+    const int dir = q >> 4, jt = q & 15;                 // 16 workgroups per (XCD, direction); column tile jt: units jt*16 .. jt*16 + 15
     const int B = p.B, T = p.T, b0 = xcd * 4;
-    const int jt = m * 4 + wave;                         // this wave's column tile: units jt*16 .. jt*16 + 15
     const int u = jt * 16 + li;
     int len[4], tg = 0;
 #pragma unroll
@@ -222,66 +245,116 @@ __global__ __launch_bounds__(256) void bilstm_persist_bwd_k(BiBwdP p) {
         len[r] = (b0 + r < B) ? min(p.lens[b0 + r], T) : 0;
         tg = len[r] > tg ? len[r] : tg;
     }
-    bf16x8 w[32];
+    tg = __builtin_amdgcn_readfirstlane(tg);
+    bf16x8 w[8];                                         // k-chunks 8 wave .. 8 wave + 7 of the tile's 32
     {
         const bf16x8* wf = reinterpret_cast<const bf16x8*>(p.wTfrag[dir]);
 #pragma unroll
-        for (int c = 0; c < 32; ++c) w[c] = wf[((size_t)jt * 32 + c) * 64 + lane];
+        for (int c = 0; c < 8; ++c) w[c] = wf[((size_t)jt * 32 + wave * 8 + c) * 64 + lane];
     }
-    unsigned long long* gbase = p.gran + ((size_t)xcd * 2 + dir) * GRAN_B;          // + parity * 16 * GRAN_B
-    __amdgpu_buffer_rsrc_t rs[2];
-#pragma unroll
-    for (int par = 0; par < 2; ++par) rs[par] = __builtin_amdgcn_make_buffer_rsrc(gbase + (size_t)par * 16 * GRAN_B, 0, GRAN_B * 8, 0x00020000);
+    // ONE descriptor over both parity buffers of the group, built from scalars; parity and k-quarter select a scalar byte offset
+    unsigned long long* gbase = p.gran + ((size_t)xcd * 2 + dir) * GRAN_B;
+    constexpr int PAROFF = 16 * GRAN_B * 8;              // bytes between a group's two parity buffers
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(gbase, 0, PAROFF + GRAN_B * 8, 0x00020000);
     const int voff = lane * 16;
+    const int soff_w = wave * 4096;                      // load groups 2 wave, 2 wave + 1
     const long t_start = wall_clock64();
-    // As in the forward kernel, one shuffle per row hands row r of the MFMA result (register r of lanes 0..15, lane <-> unit) to
-    // the lane group kg = r: every lane finishes ONE (row, unit) element -- six row loads, one cell backward, four granule and
-    // four dgx stores per lane and step instead of four times as many.
+    // wave 0: lane (kg, li) finishes element (row kg, unit u) of the tile
+    const bool fin = wave == 0;
     const int mylen = kg == 0 ? len[0] : kg == 1 ? len[1] : kg == 2 ? len[2] : len[3];
     const float* gp = p.gates[dir];
     const float* cp = p.cell[dir];
     struct Rows { float g[4]; float dy; float cprev; };
-    auto load_rows = [&](int t, Rows& v) {               // saved gates i f g o, dy, and the cell of the recurrence's previous step
+    // saved gates i f g o, dy, and the cell of the recurrence's previous step.  The loads are unconditional, from clamped (always
+    // valid) addresses -- a load under a lane mask comes with a default value in its register, and the copies the compiler makes of
+    // those wait for loads that were only just issued.  What a row reads outside [0, len) is masked where it is used (see step).
+    const int brow = min(b0 + kg, B - 1);
+    auto load_rows = [&](int t, Rows& v) {
         const int tp = dir ? t + 1 : t - 1;              // the recurrence's previous step in time
-        const bool on = t >= 0 && t < mylen;
-        const size_t row = (size_t)t * B + b0 + kg;
+        const size_t row = (size_t)min(max(t, 0), T - 1) * B + brow;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) v.g[g] = on ? gp[row * 4 * BH + g * BH + u] : 0.f;
-        v.dy = on ? p.dy[row * p.ldy + dir * BH + u] : 0.f;
-        // (also for a row that only joins at the walk's NEXT step: this value becomes its c_t there)
-        v.cprev = (tp >= 0 && tp < mylen) ? cp[((size_t)tp * B + b0 + kg) * BH + u] : 0.f;
+        for (int g = 0; g < 4; ++g) v.g[g] = gp[row * 4 * BH + g * BH + u];
+        v.dy = p.dy[row * p.ldy + dir * BH + u];
+        v.cprev = cp[((size_t)min(max(tp, 0), T - 1) * B + brow) * BH + u];
     };
-    // backward walks the recurrence the other way round: forward direction t = tg-1 .. 0, reverse direction t = 0 .. tg-1
-    Rows cur, nxt;
+    const bool prof = PROF && p.prof != nullptr && xcd == 0 && q == 0 && lane == 0;
+    // backward walks the recurrence the other way round: forward direction t = tg-1 .. 0, reverse direction t = 0 .. tg-1.
+    // The rows of step s + 1 are in flight while step s runs.  They live in two register sets that swap roles from step to step (the
+    // loop below is written out for two steps): a copy from one set to the other would have to wait for the loads it copies.
+    Rows ra, rb;
     const int t0 = dir ? 0 : tg - 1;
-    load_rows(t0, cur);
-    float c_t = (t0 >= 0 && t0 < mylen) ? cp[((size_t)t0 * B + b0 + kg) * BH + u] : 0.f, dc_carry = 0.f;
+    float c_t = 0.f, dc_carry = 0.f;
+    if (fin) {
+        load_rows(t0, ra);
+        if (t0 >= 0 && t0 < mylen) c_t = cp[((size_t)t0 * B + b0 + kg) * BH + u];
+    }
     bool dead = false;
-    for (int s = 0; s < tg; ++s) {
-        const int t = dir ? s : tg - 1 - s;
-        f32x4 acc = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (s > 0) {
-            // the group's whole dgates vector (16 KB of tagged granules) in one sweep: 16 x 16-byte loads in flight
-            u32x4 ld[8][2];
-            if (!poll<8>(ld, rs[(s - 1) & 1], voff, (unsigned)s, t_start, p.timeout_ticks, p.status)) { dead = true; break; }
+    auto stamp = [&](int s, const long (&st)[6]) {
+        if constexpr (PROF) {
+            if (prof && s < 1024) {
 #pragma unroll
-            for (int c = 0; c < 32; ++c) {
-                const u32x4 pay = (u32x4){ld[c >> 2][0][0], ld[c >> 2][0][2], ld[c >> 2][1][0], ld[c >> 2][1][2]};
-                acc = mfma16(__builtin_bit_cast(bf16x8, member(pay, c & 3)), w[c], acc);
+                for (int i = 0; i < 6; ++i) p.prof[((size_t)s * 4 + wave) * 6 + i] = st[i];
             }
         }
-        if (s + 1 < tg) load_rows(dir ? t + 1 : t - 1, nxt);
-        const float x1 = __shfl(acc[1], li, 64), x2 = __shfl(acc[2], li, 64), x3 = __shfl(acc[3], li, 64);
-        const float dh_rec = kg == 0 ? acc[0] : kg == 1 ? x1 : kg == 2 ? x2 : x3;                // (row kg, unit u)
+    };
+    auto step = [&](int s, Rows& cur, Rows& nxt) __attribute__((always_inline)) -> bool {      // false: the workgroup leaves
+        const int t = dir ? s : tg - 1 - s;
+        long st[6] = {0, 0, 0, 0, 0, 0};
+        if (prof) st[0] = wall_clock64();
+        float dh_rec = 0.f;
+        if (s > 0) {
+            const int par = s & 1;
+            u32x4 ld[2][2];
+            if (!poll<2>(ld, rs, voff, (unsigned)s, t_start, p.timeout_ticks, p.status, soff_w + (par ^ 1) * PAROFF)) {
+                dead = true;
+                quit[par] = 1;
+                __syncthreads();                         // the step's barrier, on this path: the others read the flag behind theirs
+                return false;
+            }
+            // Every poll load has returned: its tags were just compared, and vmcnt retires in order, so nothing at all is in flight.
+            // Said in a form the compiler's wait-count pass sees -- the spin loop's exit shares a block with its back edge, which
+            // re-issues loads, and without this the pass waits for the row loads below wherever a register of the poll is reused: in
+            // front of the MFMAs and in the cell phase.  (The time-out path above stays apart for the same reason.)
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            if (prof) st[1] = wall_clock64();
+            if (fin && s + 1 < tg) load_rows(dir ? t + 1 : t - 1, nxt);   // a whole step ahead of the poll that queues behind it
+            f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const u32x4 pay = (u32x4){ld[c >> 2][0][0], ld[c >> 2][0][2], ld[c >> 2][1][0], ld[c >> 2][1][2]};
+                acc[c & 1] = mfma16(__builtin_bit_cast(bf16x8, member(pay, c & 3)), w[c], acc[c & 1]);
+            }
+            if (kg == 0) part[par][wave][li] = acc[0] + acc[1];      // rows 0..3 of column li sit in lanes 0..15
+            if (prof) st[2] = wall_clock64();
+            __syncthreads();
+            if (quit[par]) return false;                 // the same answer in all four waves (see above)
+            if (fin) {
+                const float* pp = reinterpret_cast<const float*>(&part[par][0][li]) + kg;
+                dh_rec = ((pp[0] + pp[64]) + pp[128]) + pp[192];     // k-quarters 0, 1, 2, 3 of (row kg, unit u)
+            }
+        } else if (fin && tg > 1) {
+            load_rows(dir ? t + 1 : t - 1, nxt);
+        }
+        if (prof) st[3] = wall_clock64();
+        if (!fin) {
+            stamp(s, st);
+            return true;
+        }
+        // the masks of the unconditional row loads: an inactive row's gates and dy only reach values that are dropped right here;
+        // the cell of the recurrence's previous step is zero where that step does not exist (also for a row that only joins at the
+        // walk's NEXT step: this value becomes its c_t there)
+        const int tp = dir ? t + 1 : t - 1;
+        const float c_prev = (tp >= 0 && tp < mylen) ? cur.cprev : 0.f;
         float da[4], carry;
-        lstm_cell_bwd<true>(dh_rec + cur.dy, dc_carry, cur.g[0], cur.g[1], cur.g[2], cur.g[3], c_t, cur.cprev, da, carry);
+        lstm_cell_bwd<true>(dh_rec + cur.dy, dc_carry, cur.g[0], cur.g[1], cur.g[2], cur.g[3], c_t, c_prev, da, carry);
         const bool active = t < mylen;
         if (active) {
             dc_carry = carry;
         } else {
 #pragma unroll
-            for (int g = 0; g < 4; ++g) da[g] = 0.f;
+            for (int g = 0; g < 4; ++g) da[g] = 0.f;     // (a row that does not take part publishes zeros)
         }
+        if (prof) st[4] = wall_clock64();
         // publish dgates_s: k = gate * H + unit, one granule per unit pair (even lanes)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -296,10 +369,29 @@ __global__ __launch_bounds__(256) void bilstm_persist_bwd_k(BiBwdP p) {
             float* dg = p.dgx[dir] + ((size_t)t * B + b0 + kg) * 4 * BH + u;
             dg[0] = da[0]; dg[BH] = da[1]; dg[2 * BH] = da[2]; dg[3 * BH] = da[3];
         }
-        c_t = cur.cprev;                                 // the cell of the step the walk visits next
-        cur = nxt;
+        c_t = c_prev;                                    // the cell of the step the walk visits next
+        if (prof) st[5] = wall_clock64();
+        stamp(s, st);
+        return true;
+    };
+    if (tg > 0) {
+        step(0, ra, rb);
+        for (int s = 1; s < tg; s += 2) {
+            if (!step(s, rb, ra)) break;
+            if (s + 1 >= tg) break;
+            if (!step(s + 1, ra, rb)) break;
+        }
     }
     if (dead && lane == 0) atomicExch(p.status, 1);
+}
+
+__global__ __launch_bounds__(256) void bilstm_persist_bwd_k(BiBwdP p) {
+    extern __shared__ float occupancy_pad[];
+    bilstm_bwd_body<false>(p);
+}
+__global__ __launch_bounds__(256) void bilstm_persist_bwd_prof_k(BiBwdP p) {
+    extern __shared__ float occupancy_pad[];
+    bilstm_bwd_body<true>(p);
 }
 
 }  // namespace
@@ -308,6 +400,8 @@ static inline size_t al256b(size_t v) { return (v + 255) & ~size_t(255); }
 constexpr size_t BI_WFRAG = (size_t)4 * BH * BH * 2;               // one direction's fragment image
 constexpr size_t BI_GRAN = (size_t)2 * 16 * GRAN_B * 8;            // the larger (backward) hand-off region
 constexpr size_t BI_LDS = 96 * 1024;                               // one workgroup per CU: the census expects 32 per XCD
+constexpr size_t BI_LDS_STATIC = 2 * 4 * 16 * 16 + 2 * 4 + 2 * 4;  // backward: part, quit; join: slot
+static_assert(BI_LDS + BI_LDS_STATIC <= 160 * 1024 && 2 * BI_LDS > 160 * 1024, "exactly one workgroup fits a CU's 160 KB of LDS");
 
 #if FT_OPFMT == 0
 extern "C" int ft_lstm_persist_supported(int B, int H);
@@ -319,8 +413,11 @@ extern "C" size_t ft_bilstm_persist_workspace_bytes(int B, int H) {
     (void)B; (void)H;
     return 2 * al256b(BI_WFRAG) + al256b(BI_GRAN) + 256;
 }
+long* ftint_bilstm_prof = nullptr;                   // shared with the fp16 build of this file
+extern "C" int ft_bilstm_persist_debug_prof(void* dev_buf) { ftint_bilstm_prof = reinterpret_cast<long*>(dev_buf); return FT_OK; }
 #else
 extern "C" int ft_bilstm_persist_supported(int B, int H);
+extern long* ftint_bilstm_prof;
 #endif
 
 extern "C" int FT_OPNAME(ft_bilstm_persist_fwd)(const float* gx_f, const float* gx_r, const float* w_hh_f, const float* w_hh_r,
@@ -338,11 +435,11 @@ extern "C" int FT_OPNAME(ft_bilstm_persist_fwd)(const float* gx_f, const float* 
     unsigned long long* gran = reinterpret_cast<unsigned long long*>(base + 2 * al256b(BI_WFRAG));
     unsigned* census = reinterpret_cast<unsigned*>(base + 2 * al256b(BI_WFRAG) + al256b(BI_GRAN));
     FT_CHECK_HIP(hipMemset2DAsync(y, (size_t)ldy * 4, 0, (size_t)2 * H * 4, (size_t)T * B, st));   // padded frames: zeros
-    // tags 0: no epoch matches (epochs start at 1); preset, with the census counters, by the first fragment kernel (WfragAux)
+    // tags 0: no epoch matches (epochs start at 1); preset, with the census counters, by the fragment kernel (WfragAux): ONE launch
+    // for both directions' images, in front of every recurrence launch
     static_assert(((size_t)2 * 16 * GRAN_F * 8) % 16 == 0, "granule buffer in 16-byte pieces");
     const WfragAux aux{reinterpret_cast<uint4*>(gran), (unsigned long)((size_t)2 * 16 * GRAN_F * 8 / 16), 0u, census};
-    hipLaunchKernelGGL(make_wfrag_fwd, dim3(256), dim3(256), 0, st, w_hh_f, wf[0], H, aux);
-    hipLaunchKernelGGL(make_wfrag_fwd, dim3(256), dim3(256), 0, st, w_hh_r, wf[1], H, WfragAux{});
+    hipLaunchKernelGGL(make_wfrag_pair<false>, dim3(512), dim3(256), 0, st, w_hh_f, w_hh_r, wf[0], wf[1], H, aux);
     BiFwdP p{{gx_f, gx_r}, lens, y, (long)ldy, {gates_f, gates_r}, {cell_f, cell_r}, {wf[0], wf[1]}, gran, status, census, T, B,
              100000000L / 2};
     FT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bilstm_persist_fwd_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BI_LDS));
@@ -369,12 +466,12 @@ extern "C" int FT_OPNAME(ft_bilstm_persist_bwd)(const float* dy, int64_t ldy, co
     FT_CHECK_HIP(hipMemsetAsync(dgx_r, 0, (size_t)T * B * 4 * H * 4, st));
     static_assert(BI_GRAN % 16 == 0, "granule buffer in 16-byte pieces");
     const WfragAux aux{reinterpret_cast<uint4*>(gran), (unsigned long)(BI_GRAN / 16), 0u, census};
-    hipLaunchKernelGGL(make_wfrag_bwd, dim3(256), dim3(256), 0, st, w_hh_f, wf[0], H, aux);
-    hipLaunchKernelGGL(make_wfrag_bwd, dim3(256), dim3(256), 0, st, w_hh_r, wf[1], H, WfragAux{});
+    hipLaunchKernelGGL(make_wfrag_pair<true>, dim3(512), dim3(256), 0, st, w_hh_f, w_hh_r, wf[0], wf[1], H, aux);
     BiBwdP p{dy, (long)ldy, lens, {gates_f, gates_r}, {cell_f, cell_r}, {dgx_f, dgx_r}, {wf[0], wf[1]}, gran, status, census, T, B,
-             100000000L / 2};
-    FT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(bilstm_persist_bwd_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BI_LDS));
-    hipLaunchKernelGGL(bilstm_persist_bwd_k, dim3(NWG), dim3(256), BI_LDS, st, p);
+             100000000L / 2, ftint_bilstm_prof};
+    auto kern = p.prof ? bilstm_persist_bwd_prof_k : bilstm_persist_bwd_k;
+    FT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BI_LDS));
+    hipLaunchKernelGGL(kern, dim3(NWG), dim3(256), BI_LDS, st, p);
     FT_CHECK_LAUNCH();
     return FT_OK;
 }

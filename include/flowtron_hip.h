@@ -393,12 +393,16 @@ int ft_lstm_bidir_seq_bwd(const float* dy, int64_t ldy, const float* w_hh_f, con
                           float* dgx_f, float* dgx_r, void* work_f, void* work_r, int T, int B, int H, void* stream);
 
 /* Persistent form of ft_lstm_bidir_seq_* for the text encoder's shape (H == 256, B <= 32, 256-CU device, 16-bit operands): ONE launch
- * per pass for both directions and all time steps (csrc/bilstm_persist.hip: every wave an independent agent, no workgroup-level
- * step, XCD-local hand-off).  Same tensors as ft_lstm_bidir_seq_*; one workspace (ft_bilstm_persist_workspace_bytes, 256-byte
- * aligned); `status` as for ft_lstm_persist_*.  Same operand rounding as the launch-per-step chain, different fp32 summation order
- * (K is not split over waves): results agree to rounding, not bit for bit. */
+ * per pass for both directions and all time steps (csrc/bilstm_persist.hip: XCD-local hand-off; forward, every wave an independent
+ * agent with no workgroup-level step; backward, K split over the four waves of a workgroup and summed in a fixed order).  Same
+ * tensors as ft_lstm_bidir_seq_*; one workspace (ft_bilstm_persist_workspace_bytes, 256-byte aligned); `status` as for
+ * ft_lstm_persist_*.  Same operand rounding as the launch-per-step chain, different fp32 summation order: results agree to
+ * rounding, not bit for bit.  Deterministic; a row's results do not depend on the other rows of its batch. */
 int ft_bilstm_persist_supported(int B, int H);
 size_t ft_bilstm_persist_workspace_bytes(int B, int H);
+/* debug: device buffer [1024][4][6] int64 that subsequent ft_bilstm_persist_bwd launches fill with the stage stamps (100 MHz wall
+ * clock: step top, polled, partial written, reduced, cell done, published) of the four waves of one workgroup; NULL switches it off */
+int ft_bilstm_persist_debug_prof(void* dev_buf);
 int ft_bilstm_persist_fwd(const float* gx_f, const float* gx_r, const float* w_hh_f, const float* w_hh_r, const int32_t* lens,
                           float* y, int64_t ldy, float* gates_f, float* gates_r, float* cell_f, float* cell_r,
                           void* work, int32_t* status, int T, int B, int H, void* stream);

@@ -181,6 +181,7 @@ SIGNATURES = {
     "ft_decode_batch_gran_bytes": ([_i], _sz),
     "ft_decode_flow_batch": ([C.POINTER(DecodeBatchArgs), _p], _i),
     "ft_decode_flow_batch_keys": ([C.POINTER(DecodeBatchArgs), _p, _p], _i),
+    "ft_decode_flow_batch_forced": ([C.POINTER(DecodeBatchArgs), _p, _p], _i),
     "ft_stft_mel": ([_p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
     "ft_stft_r8": ([_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
     "ft_stft_r8_ragged": ([_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p], _i),

@@ -873,7 +873,9 @@ int make_wimg(const ft_decode_args* a, int n_layers, const unsigned short** img,
     for (int k = 0; k < 10; ++k) {
         FT_CHECK_ARG(reinterpret_cast<uintptr_t>(src[k]) % 16 == 0);
         bf16_t* d = reinterpret_cast<bf16_t*>(wp);
-        if (round) hipLaunchKernelGGL(f32_to_bf16_k, dim3(1024), dim3(256), 0, st, src[k], d, n[k]);
+        // (w_query may be null in a forced decode, which reads no query rows: its image slot is then left as it is)
+        FT_CHECK_ARG(src[k] || k == 2);
+        if (round && src[k]) hipLaunchKernelGGL(f32_to_bf16_k, dim3(1024), dim3(256), 0, st, src[k], d, n[k]);
         img[k] = d;
         wp += (n[k] * 2 + 255) & ~size_t(255);
     }

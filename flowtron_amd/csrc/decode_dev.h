@@ -1,5 +1,5 @@
 // Parameter block of the decode kernels and the bf16 chunk product (csrc/decode.hip, csrc/decode_batch.hip).
-// Included inside the anonymous namespace of decode.hip and decode_batch.hip.
+// Included inside the anonymous namespace of decode.hip, decode_batch.hip and decode_forced.hip.
 #pragma once
 
 typedef unsigned short bf16_t;

@@ -1,6 +1,6 @@
 // Hand-off protocol and weight-row helpers of the persistent decode kernels: dec_persist_k (csrc/decode.hip) and
-// dec_persist_batch_k (csrc/decode_batch.hip) share them, so a batched utterance runs the same floating-point operations.
-// Included inside the anonymous namespace of decode.hip and decode_batch.hip.
+// dec_persist_batch_k (csrc/decode_batch_k.h; decode_batch.hip, decode_forced.hip) share them, so a batched utterance runs the same floating-point operations.
+// Included inside the anonymous namespace of decode.hip, decode_batch.hip and decode_forced.hip.
 #pragma once
 
 struct DecP {

@@ -459,14 +459,19 @@ class AR_Step(nn.Module):
         attn_rows = [attn_all[i].reshape(1, 1, Lk) for i in range(n)]
         return mel, attn_rows
 
-    def infer_batch(self, x, text, lens, in_lens=None):
+    def infer_batch(self, x, text, lens, in_lens=None, forced=None):
         """Sequential inverse of a batch whose utterances have their own lengths: x [T,B,M] (utterance b's frames 0 .. lens[b]-1;
         the frames behind are not read), text [L,B,E] (utterance b's positions 0 .. in_lens[b]-1, None = all L; the positions behind
         are not read).  Groups of up to ft_decode_batch_max() utterances decode in ONE persistent launch (csrc/decode_batch.hip
-        dec_persist_batch_k; ft_decode_flow_batch_keys where a group's texts differ in length), a group of one on ft_decode_flow;
-        every utterance bit for bit as infer() decodes it alone.  Returns (out [T',B,M] zeros behind each utterance's end, attention
+        dec_persist_batch_k; ft_decode_flow_batch_keys where a group's texts differ in length), a group of one on ft_decode_flow
+        (with `forced`, below, on the batched launch as well); every utterance bit for bit as infer() decodes it alone.  Returns (out [T',B,M] zeros behind each utterance's end, attention
         rows [T',B,1,L] zeros behind its end and its text, frames per utterance).  The caller has checked the geometry
-        (Flowtron._batch_decode_usable)."""
+        (Flowtron._batch_decode_usable).
+        forced [B,T,L] (utterance-major, as the launch reads it): GIVEN attention rows, in THIS flow's time order -- utterance b
+        decodes along forced[b, :lens[b], :in_lens[b]], nothing behind is read.  Every group, a group of one included, then goes
+        through ft_decode_flow_batch_forced (csrc/decode_forced.hip): no query projection, scores or softmax, only V is projected,
+        and the returned attention rows are the given ones.  Bit for bit independent of the grouping; NOT bit-identical to
+        infer(attns=), whose staged chain sums in another order."""
         T, B, M = x.shape
         Lk = text.shape[0]
         il = list(in_lens) if in_lens is not None else [Lk] * B
@@ -499,7 +504,7 @@ class AR_Step(nn.Module):
         singles, batched = [], []
         for g0 in range(0, B, NB):
             g = list(range(g0, min(g0 + NB, B)))
-            if len(g) == 1:
+            if len(g) == 1 and forced is None:
                 singles.append(g[0])
                 continue
             batched.append(g)
@@ -519,15 +524,24 @@ class AR_Step(nn.Module):
             for j, b in enumerate(g):
                 # the projections of infer(), one utterance at a time over its own positions (rows behind them are not read)
                 tb = text[:il[b], b:b + 1].contiguous()
-                K[j, :il[b]].copy_(ops.linear(tb, att.key.linear_layer.weight, None).reshape(il[b], A))
+                if forced is None:
+                    K[j, :il[b]].copy_(ops.linear(tb, att.key.linear_layer.weight, None).reshape(il[b], A))
                 V[j, :il[b]].copy_(ops.linear(tb, att.value.linear_layer.weight, None).reshape(il[b], A))
             res.copy_(x[:Ng, g0:g0 + nb].transpose(0, 1))
             mel_out.zero_()                                      # rows past an utterance's end are not written
             attn_out.zero_()
             n_lim = lim_all[g0:g0 + nb]
+            rows = None
+            if forced is not None:
+                # [nb][Ng][Lk] in a buffer of the group's own: the entry wants 16-byte aligned rows, and `forced` may be a view
+                # at any offset of the caller's tensor (a flow's slice of [F,B,N,L], a sliced batch)
+                rows = bufs.get("forced")
+                if rows is None:
+                    rows = bufs["forced"] = torch.empty(nb, Ng, Lk, **f32)
+                rows.copy_(forced[g0:g0 + nb, :Ng])
             args = L.DecodeArgs(
                 L.ptr(a.weight_ih_l0), L.ptr(a.weight_hh_l0), L.ptr(a.bias_ih_l0), L.ptr(a.bias_hh_l0),
-                L.ptr(att.query.linear_layer.weight), L.ptr(att.v.linear_layer.weight), L.ptr(K), L.ptr(V),
+                L.ptr(att.query.linear_layer.weight), L.ptr(att.v.linear_layer.weight), L.ptr(K) if forced is None else None, L.ptr(V),
                 L.ptr(p.weight_ih_l0), L.ptr(p.weight_hh_l0), L.ptr(p.bias_ih_l0), L.ptr(p.bias_hh_l0),
                 L.ptr(p.weight_ih_l1), L.ptr(p.weight_hh_l1), L.ptr(p.bias_ih_l1), L.ptr(p.bias_hh_l1),
                 L.ptr(d[0].linear_layer.weight), L.ptr(d[0].linear_layer.bias),
@@ -538,12 +552,14 @@ class AR_Step(nn.Module):
                 L.ptr(res), L.ptr(mel_out), L.ptr(attn_out), L.ptr(n_done), None,
                 0, Ng, Lk, H, A, M, float(att.temperature),
                 float(self.gate_threshold) if has_gate else 2.0, 0,
-                None, None, None, None, None, None, 1, None, None,
+                None, None, None, None, None, None, 1, None, L.ptr(rows),
                 L.ptr(wimg), wimg.numel() if wimg is not None else 0, L.ptr(gran), L.ptr(ops.persist_status(dev)), 2, None)
             bargs = L.DecodeBatchArgs(args, nb, L.ptr(n_lim), int(len(batched) > 1))
-            if any(il[b] < Lk for b in g):                       # texts of different lengths: a key count per utterance
-                L.check(L.lib().ft_decode_flow_batch_keys(C.byref(bargs), L.ptr(keys_all[g0:g0 + nb]), L.stream()),
-                        "ft_decode_flow_batch_keys")
+            keys = L.ptr(keys_all[g0:g0 + nb]) if any(il[b] < Lk for b in g) else None
+            if forced is not None:
+                L.check(L.lib().ft_decode_flow_batch_forced(C.byref(bargs), keys, L.stream()), "ft_decode_flow_batch_forced")
+            elif keys is not None:                               # texts of different lengths: a key count per utterance
+                L.check(L.lib().ft_decode_flow_batch_keys(C.byref(bargs), keys, L.stream()), "ft_decode_flow_batch_keys")
             else:
                 L.check(L.lib().ft_decode_flow_batch(C.byref(bargs), L.stream()), "ft_decode_flow_batch")
             # copied out on the stream: the next group may reuse these buffers
@@ -557,10 +573,11 @@ class AR_Step(nn.Module):
                 n = n_done_all.tolist()                          # the flow's one host read
             if not ok:
                 # a batched launch did not complete: the device now uses the staged kernels, and these groups decode again one
-                # utterance at a time (infer() keeps its own fallback)
+                # utterance at a time (infer() keeps its own fallback; given rows: its staged forced decode)
                 singles = sorted(singles + [b for g in batched for b in g])
         for b in singles:
-            m_, rows = self.infer(x[:lens[b], b:b + 1].contiguous(), text[:il[b], b:b + 1].contiguous())
+            m_, rows = self.infer(x[:lens[b], b:b + 1].contiguous(), text[:il[b], b:b + 1].contiguous(),
+                                  None if forced is None else forced[b, :lens[b], :il[b]].contiguous().float())
             n[b] = m_.shape[0]
             out[:, b] = 0.0
             attn[:, b] = 0.0
@@ -616,6 +633,22 @@ def lengths_arg(v, name, B, hi):
     if any(not 1 <= x <= hi for x in vals):
         raise ValueError("%s must lie in 1 ..= %d, got %r" % (name, hi, vals))
     return vals
+
+
+def aligned_rows(alignment, flow, n_frames, n_text):
+    """The rows flow `flow` decodes along, for a whole batch and in that flow's own time order: alignment [B, N, L] (every flow)
+    or [F, B, N, L] (one per flow) in natural time, n_frames: list of B -> float32 [B, max(n_frames), n_text] with
+    rows[b, :n_frames[b]] = alignment[.., b, :n_frames[b], :n_text], for an odd (reversed) flow flipped over the utterance's own
+    n_frames[b] -- what infer_aligned's utterance loop hands infer(attns=).  Rows behind n_frames[b] are not meant to be read.
+    One gather on the tensor's device, no host loop; plain torch, so it runs on CPU tensors as well."""
+    a = alignment[flow] if alignment.dim() == 4 else alignment
+    n = max(n_frames)
+    a = a[:, :n, :n_text]
+    if flow % 2 == 1:
+        nf = torch.tensor(n_frames, device=a.device)[:, None]
+        t = torch.arange(n, device=a.device)[None, :]
+        a = torch.gather(a, 1, torch.where(t < nf, nf - 1 - t, t)[:, :, None].expand(-1, -1, a.shape[2]))
+    return a.float().contiguous()
 
 
 # --------------------------------------------------------------------------
@@ -788,7 +821,7 @@ class Flowtron(nn.Module):
             return z, maps[0], maps[1]
 
     def infer_aligned(self, residual, speaker_ids, text, alignment, in_lens=None, n_frames=None, temperature=1.0,
-                      gate_threshold=1.0):
+                      gate_threshold=1.0, persistent=False):
         """Decodes a batch along GIVEN alignments (durations from flowtron_amd.align, or the soft maps of alignments()):
         residual [B, M, N], text [B, L], alignment [B, N, L] (used by every flow) or [F, B, N, L] (one per flow), hard or soft,
         ALWAYS in natural time -- the rows of an odd flow are flipped here, over the utterance's own frames.  in_lens [B]: text
@@ -796,7 +829,16 @@ class Flowtron(nn.Module):
         Utterance b is decoded exactly as infer(residual[b:b+1, :, :n_b], speaker_ids[b:b+1], text[b:b+1, :L_b], attns=[its rows
         per flow, in the flow's own time order], gate_threshold=...) decodes it: a loop over the staged forced-decode chain.
         gate_threshold 1.0 (the default) lets the alignment decide the length; a lower one lets the gate cut it.
-        -> (mel [B, M, N'] with zeros behind each utterance's frames, lengths: CPU int64 [B])."""
+        -> (mel [B, M, N'] with zeros behind each utterance's frames, lengths: CPU int64 [B]).
+        persistent=True: the batch decodes flow by flow in groups of up to ft_decode_batch_max() utterances per persistent launch
+        (AR_Step.infer_batch(forced=), csrc/decode_forced.hip) where _batch_decode_usable holds -- the geometry of the batched
+        launch on a device whose persistent kernels work; FLOWTRON_DECODE_PERSIST=0 or FLOWTRON_DECODE_BATCH=0 switch it off --
+        and takes the loop above otherwise, silently, as infer treats a batch.  Every flow gets the same rows as in the loop
+        (aligned_rows: an odd flow's flipped over the GIVEN n_frames[b], of which the frames a gate left are the first).
+        Guaranteed then: each utterance is bit for bit what it is when decoded alone with persistent=True, whatever the batch
+        and the grouping; each flow is within 10 x the fp32 reference implementation's own deviation from a float64 decode of
+        the same inputs (tests/test_gpu_decode_aligned.py), as the staged result is.  It is NOT bit-identical to
+        persistent=False: the persistent kernels sum in another order than the staged chain."""
         L.require_cuda(residual, text, alignment)
         if residual.dim() != 3 or text.dim() != 2 or text.shape[0] != residual.shape[0]:
             raise ValueError("residual must be [B, M, N] and text [B, L] with the same B, got %s and %s"
@@ -808,6 +850,9 @@ class Flowtron(nn.Module):
         il = lengths_arg(in_lens, "in_lens", B, Lt) or [Lt] * B
         nf = lengths_arg(n_frames, "n_frames", B, N) or [N] * B
         sid = speaker_ids.reshape(B, -1)
+        if persistent and self._batch_decode_usable(residual, max(il)):
+            mel, _, n = self._infer_batched(residual, sid, text, temperature, gate_threshold, il, nf, alignment)
+            return mel, torch.tensor(n, dtype=torch.int64)
         outs = []
         for b in range(B):
             rows = []
@@ -904,11 +949,13 @@ class Flowtron(nn.Module):
         return (st.n_lstm_layers == 2 and not st.use_cumm_attention and H == 1024 and A == 640 and residual.shape[1] == 80
                 and residual.shape[2] >= 1 and 1 <= n_text <= 1024 and ops.persist_usable(residual.device))
 
-    def _infer_batched(self, residual, sid, text, temperature, gate_threshold, in_lens, out_lens):
+    def _infer_batched(self, residual, sid, text, temperature, gate_threshold, in_lens, out_lens, alignment=None):
         """infer() of a batch, flow by flow, each flow in groups of up to ft_decode_batch_max() utterances per persistent launch.
         Every utterance keeps its own text (in_lens: its own encoder call, keys and values) and its own length between flows
         (out_lens, then its own gate stop; the reversed flows flip its own frames), so each comes out exactly as decoded alone.
-        Returns infer()'s batch format and the frames of each utterance."""
+        Returns infer()'s batch format and the frames of each utterance.
+        alignment (infer_aligned's, natural time): every flow decodes along its rows (aligned_rows over out_lens); the attention
+        rows, which are the given ones, are then not returned (None)."""
         B, Lt = residual.shape[0], text.shape[1]
         Lk = max(in_lens)                                        # the text, padded to its longest utterance only
         with torch.no_grad():
@@ -922,19 +969,23 @@ class Flowtron(nn.Module):
             x = residual[:, :, :max(out_lens)].permute(2, 0, 1).contiguous().float()    # (frames past out_lens[b] are never read)
             lens = list(out_lens)
             atts = []
-            for flow in reversed(self.flows):
+            for f in reversed(range(len(self.flows))):
+                flow = self.flows[f]
                 self.set_temperature_and_gate(flow, temperature, gate_threshold)
                 back = hasattr(flow, "ar_step")
                 st = flow.ar_step if back else flow
                 if back:                                         # flowtron.py:631-633 per utterance: flip its own frames
                     x = ops.reverse_by_length(x, torch.tensor(lens, dtype=torch.int32, device=x.device), True)
-                x, aw, lens = st.infer_batch(x, enc, lens, in_lens)
+                x, aw, lens = st.infer_batch(x, enc, lens, in_lens,
+                                             None if alignment is None else aligned_rows(alignment, f, out_lens, Lk))
                 if back:
                     x = ops.reverse_by_length(x, torch.tensor(lens, dtype=torch.int32, device=x.device), True)
                 atts.append(aw)
             n = max(lens)
             mel = residual.new_zeros(B, x.shape[2], n, dtype=torch.float32)
             mel.copy_(x[:n].permute(1, 2, 0))
+            if alignment is not None:
+                return mel, None, lens
             rows = []
             for aw in atts:
                 a_ = residual.new_zeros(n, B, 1, Lt, dtype=torch.float32)

@@ -544,7 +544,17 @@ int ft_decode_flow(const ft_decode_args* a, void* stream);
  * ft_decode_flow_batch_keys: the same with a text length per utterance.  n_keys [nb] (device int32, each 1 ..= a.L; 4-byte
  * aligned): utterance b attends to key / value rows 0 .. n_keys[b]-1 of its K, V only, exactly as ft_decode_flow decodes it alone
  * at L = n_keys[b]; its attn_out columns >= n_keys[b] are not written (row stride stays a.L).  NULL = a.L for every utterance,
- * which is ft_decode_flow_batch. */
+ * which is ft_decode_flow_batch.
+ * ft_decode_flow_batch_forced: 1 .. ft_decode_batch_max() utterances ALONG GIVEN ALIGNMENT ROWS, in the same launch geometry (a
+ * group of one included).  a.forced (required) is nb-strided like the other per-utterance operands: [nb][N][L] fp32, 16-byte
+ * aligned, frame i of utterance b at forced[(b * N + i) * L], rows in the flow's own time order (a reversed flow's rows
+ * reversed by the caller).  A frame takes its row as it is -- no scores, no softmax, no normalisation (what ft_decode_flow does
+ * with a.forced) --, writes it verbatim to attn_out and multiplies it with V; columns >= n_keys[b] and rows >= n_lim[b] are never
+ * read.  n_keys, n_lim, gate stops, wimg / wimg_ready, persist_gran and persist_status as above.  a.w_query and a.K may be NULL
+ * (not read); a.temperature is accepted and unused.  With a.w_query NULL the query image slot of a.wimg is NOT written: a later
+ * free-running call on the same a.wimg must round again (wimg_ready = 0), or it reads whatever the slot held.  FT_EUNSUPPORTED: nb < 1 or > ft_decode_batch_max(), a.forced NULL, a.prior
+ * given, or outside the persistent geometry as above.  The result is the float arithmetic of the free-running launch on the given
+ * rows, not that of ft_decode_flow's staged forced decode: the two sum in different orders. */
 typedef struct {
     ft_decode_args a;
     int nb;
@@ -555,6 +565,7 @@ int ft_decode_batch_max(void);
 size_t ft_decode_batch_gran_bytes(int nb);
 int ft_decode_flow_batch(const ft_decode_batch_args* a, void* stream);
 int ft_decode_flow_batch_keys(const ft_decode_batch_args* a, const int32_t* n_keys, void* stream);
+int ft_decode_flow_batch_forced(const ft_decode_batch_args* a, const int32_t* n_keys, void* stream);
 
 /* ---- STFT magnitude + mel + log (audio_processing.py:117-134, 207-235) -------
  * y [B,N] in [-1,1] -> mel [B,n_mel,N/hop+1]; window [n_fft] (periodic hann),

@@ -11,10 +11,10 @@ import torch
 
 from flowtron_amd.model import (AR_Back_Step, AR_Step, Attention, AttentionConditioningLayer, AttentionCTCLoss, ConvNorm,
                                 DenseLayer, Encoder,
-                                Flowtron, FlowtronLoss, LinearNorm, MaskedInstanceNorm1d)
+                                Flowtron, FlowtronLoss, GaussianMixture, LinearNorm, MaskedInstanceNorm1d, MelEncoder)
 
 for _cls in (AR_Back_Step, AR_Step, Attention, AttentionConditioningLayer, AttentionCTCLoss, ConvNorm, DenseLayer, Encoder, Flowtron,
-             FlowtronLoss, LinearNorm, MaskedInstanceNorm1d):
+             FlowtronLoss, GaussianMixture, LinearNorm, MaskedInstanceNorm1d, MelEncoder):
     _cls.__module__ = "flowtron"          # pickled checkpoints resolve `flowtron.<Class>`
 
 

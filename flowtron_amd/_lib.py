@@ -210,7 +210,16 @@ SIGNATURES = {
     "ft_radam_step": ([_p, _p, _p, _p, _l, _p, _d, _d, _d, _d, _d, _d, _d, _i, _p, _p], _i),
     "ft_radam_step_dev": ([_p, _p, _p, _p, _l, _p, _d, _d, _d, _d, _d, _d, _i, _p, _p], _i),
     "ft_poison_if_nonzero": ([_p, _p, _p], _i),
+    "ft_mixture_nll_work_floats": ([_i, _i, _i, _i], _sz),
+    "ft_mixture_nll_fwd": ([_p] * 5 + [_i, _l] + [_p] * 4 + [_i] * 5 + [_p], _i),
+    "ft_mixture_nll_bwd": ([_p] * 13 + [_i] * 5 + [_p], _i),
+    "ft_time_pool_fwd": ([_p, _p, _p, _i, _i, _i, _p], _i),
+    "ft_time_pool_bwd": ([_p, _p, _p, _i, _i, _i, _p], _i),
+    "ft_softmax_rows_fwd": ([_p, _p, _i, _i, _p], _i),
+    "ft_softmax_rows_bwd": ([_p, _p, _p, _i, _i, _p], _i),
+    "ft_mixture_sample": ([_p] * 6 + [_i] * 5 + [_f, _p], _i),
 }
+MIXTURE_MAX_C = 64         # FT_MIXTURE_MAX_C
 
 # fp16-operand twins (include/flowtron_hip.h, end): same signatures, suffix _f16
 OP16_TWINS = ("ft_gemm", "ft_bf16_image", "ft_bf16_image_colsum", "ft_bf16_image_colsum_acc", "ft_bf16_image_rows_acc", "ft_bf16_image_rows_act_bwd_acc", "ft_gemm_img", "ft_bf16_image_rows", "ft_bf16_image_rows_into", "ft_bf16_image_rows_act_bwd", "ft_img_gemv_rows", "ft_img_gemv_rows_bwd", "ft_lstm_seq_fwd", "ft_lstm_seq_bwd",

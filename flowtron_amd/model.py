@@ -14,6 +14,7 @@ import numbers
 import os
 from typing import List, Optional
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -78,6 +79,27 @@ class DenseLayer(nn.Module):
         return x
 
 
+def encoder_operand_modes():
+    """(conv_mode, lstm_mode) of the text encoder -- and of the mel encoder, which follows it -- for the current operand mode."""
+    # FLOWTRON_ENCODER_F32 = conv | all: the encoder's convolutions (and its BiLSTM) with fp32 operands inside a 16-bit step -- 2 % of
+    # the step's FLOPs; measures how much of the 16-bit gradient noise of the embedding / encoder parameters is made HERE (VERDICT r4 #6)
+    enc32 = os.environ.get("FLOWTRON_ENCODER_F32", "")
+    conv_mode = L.FT_F32 if enc32 in ("conv", "all") else None
+    lstm_mode = L.FT_F32 if enc32 == "all" else None
+    m16 = L.mfma_mode()
+    if L.is16(m16) and enc32 in ("fwd", "dx", "dw", "fwd+dx"):      # one GEMM of the three in fp32 operands (which one makes the noise?)
+        conv_mode = (L.FT_F32 if "fwd" in enc32 else m16, L.FT_F32 if "dx" in enc32 else m16, L.FT_F32 if "dw" in enc32 else m16)
+    elif L.is16(m16) and enc32 in ("", "split"):
+        # DEFAULT in the 16-bit modes (round 5): the convolutions' FORWARD products at fp32 grade from split images (x = hi + lo:
+        # one 16-bit GEMM over [hi | lo | hi] x [hi | hi | lo], ops.Bf16Image.split3), backward in the step's 16-bit format.
+        # Measured on the bench batch: the 16-bit rounding of these three forward GEMMs -- renormalised by the instance norm
+        # behind each -- was what made the text-embedding / encoder gradients deviate 0.11 from the fp32 oracle (the real
+        # reference under bf16 autocast: 0.17); with fp32-grade forward products the worst gradient of the model reads 0.008.
+        # fp32 operands for the input or the weight gradients instead change nothing (0.113).  FLOWTRON_ENCODER_F32=off: 16-bit.
+        conv_mode = ("split3", m16, m16)
+    return conv_mode, lstm_mode
+
+
 # --------------------------------------------------------------------------
 # Encoder -- flowtron.py:467-525
 # --------------------------------------------------------------------------
@@ -98,22 +120,7 @@ class Encoder(nn.Module):
 
     def _run(self, x, lens):
         """x [L,B,C] time-major, lens int32 [B] -> [L,B,C]."""
-        # FLOWTRON_ENCODER_F32 = conv | all: the encoder's convolutions (and its BiLSTM) with fp32 operands inside a 16-bit step -- 2 % of
-        # the step's FLOPs; measures how much of the 16-bit gradient noise of the embedding / encoder parameters is made HERE (VERDICT r4 #6)
-        enc32 = os.environ.get("FLOWTRON_ENCODER_F32", "")
-        conv_mode = L.FT_F32 if enc32 in ("conv", "all") else None
-        lstm_mode = L.FT_F32 if enc32 == "all" else None
-        m16 = L.mfma_mode()
-        if L.is16(m16) and enc32 in ("fwd", "dx", "dw", "fwd+dx"):      # one GEMM of the three in fp32 operands (which one makes the noise?)
-            conv_mode = (L.FT_F32 if "fwd" in enc32 else m16, L.FT_F32 if "dx" in enc32 else m16, L.FT_F32 if "dw" in enc32 else m16)
-        elif L.is16(m16) and enc32 in ("", "split"):
-            # DEFAULT in the 16-bit modes (round 5): the convolutions' FORWARD products at fp32 grade from split images (x = hi + lo:
-            # one 16-bit GEMM over [hi | lo | hi] x [hi | hi | lo], ops.Bf16Image.split3), backward in the step's 16-bit format.
-            # Measured on the bench batch: the 16-bit rounding of these three forward GEMMs -- renormalised by the instance norm
-            # behind each -- was what made the text-embedding / encoder gradients deviate 0.11 from the fp32 oracle (the real
-            # reference under bf16 autocast: 0.17); with fp32-grade forward products the worst gradient of the model reads 0.008.
-            # fp32 operands for the input or the weight gradients instead change nothing (0.113).  FLOWTRON_ENCODER_F32=off: 16-bit.
-            conv_mode = ("split3", m16, m16)
+        conv_mode, lstm_mode = encoder_operand_modes()
         drawn = None
         if self.dropout_masks is None and self.training:
             # F.dropout(p=0.5) keep-masks (flowtron.py:502) of ALL conv layers in one draw: two kernels per step instead of four per layer
@@ -140,6 +147,107 @@ class Encoder(nn.Module):
         xt = x.permute(2, 0, 1).contiguous()
         lens = torch.full((xt.shape[1],), xt.shape[0], dtype=torch.int32, device=xt.device)
         return self._run(xt, lens).transpose(0, 1)
+
+
+# --------------------------------------------------------------------------
+# Gaussian-mixture prior: MelEncoder + GaussianMixture -- flowtron.py:366-450, 312-363
+# --------------------------------------------------------------------------
+class MelEncoder(nn.Module):
+    """flowtron.py:366-450: two stages of Conv1d(k 3) + masked instance norm + ReLU + dropout 0.5 (80 -> C', C' -> C'), a packed
+    BiLSTM (C' -> 2 x C'/2) and the mean over the time axis of its zero-padded output (:437-439) -- whose divisor is therefore the
+    batch's LONGEST length, not the utterance's own (ops.TimePoolFn takes it from the lengths on the device).  A batch of one runs
+    the unmasked norm (:417), the same formula over all its frames.  The reference zero-fills the caller's mel behind the lengths in
+    place (:420); here the input is only read -- the kernels never look behind a length.  The convolutions follow the text
+    encoder's operand-mode choice (encoder_operand_modes)."""
+
+    def __init__(self, encoder_embedding_dim=512, encoder_kernel_size=3, encoder_n_convolutions=2, norm_fn=MaskedInstanceNorm1d):
+        super().__init__()
+        convs = []
+        for i in range(encoder_n_convolutions):
+            convs.append(nn.Sequential(
+                ConvNorm(80 if i == 0 else encoder_embedding_dim, encoder_embedding_dim, kernel_size=encoder_kernel_size, stride=1,
+                         padding=int((encoder_kernel_size - 1) / 2), dilation=1, w_init_gain="relu"),
+                norm_fn(encoder_embedding_dim, affine=True)))
+        self.convolutions = nn.ModuleList(convs)
+        self.lstm = nn.LSTM(encoder_embedding_dim, int(encoder_embedding_dim / 2), 1, bidirectional=True)
+        self.dropout_masks = None     # test hook: list of keep-masks [T,B,C'] already scaled by 1/(1-p), one per convolution
+
+    def _run(self, x, lens):
+        """x [T,B,80] time-major, lens int32 [B] -> the BiLSTM's outputs [T,B,C']"""
+        conv_mode, lstm_mode = encoder_operand_modes()
+        drawn = None
+        if self.dropout_masks is None and self.training:
+            Cp = self.convolutions[0][0].conv.weight.shape[0]
+            drawn = torch.empty((len(self.convolutions),) + tuple(x.shape[:2]) + (Cp,), device=x.device,
+                                dtype=torch.float32).bernoulli_(0.5).mul_(2.0)
+        for i, (conv, norm) in enumerate(self.convolutions):
+            keep = None
+            if self.dropout_masks is not None:
+                keep = self.dropout_masks[i]
+            elif drawn is not None:
+                keep = drawn[i]
+            x = ops.conv_norm_relu(x, lens, conv.conv.weight, conv.conv.bias, norm.weight, norm.bias, keep, norm.eps, mode=conv_mode)
+        p = self.lstm
+        return ops.bilstm_layer(x, lens, (p.weight_ih_l0, p.weight_hh_l0, p.bias_ih_l0, p.bias_hh_l0),
+                                (p.weight_ih_l0_reverse, p.weight_hh_l0_reverse, p.bias_ih_l0_reverse, p.bias_hh_l0_reverse), mode=lstm_mode)
+
+    def forward(self, x, lens):
+        """x [B,80,T] (reference layout; not modified), lens [B] -> [B,C']"""
+        L.require_cuda(x, lens)
+        lens32 = ops.lens32(lens)
+        h = self._run(x.permute(2, 0, 1).contiguous().float(), lens32)
+        return ops.TimePoolFn.apply(h, lens32)
+
+    def infer(self, x):
+        """x [B,80,T], every frame valid -> the BiLSTM's outputs [B,T,C'] (flowtron.py:441-450, which nothing in the reference calls:
+        it hands the batch-major tensor to a time-major LSTM; the evident intent -- one output row per frame -- is implemented)"""
+        L.require_cuda(x)
+        xt = x.permute(2, 0, 1).contiguous().float()
+        lens = torch.full((xt.shape[1],), xt.shape[0], dtype=torch.int32, device=xt.device)
+        return self._run(xt, lens).transpose(0, 1)
+
+
+class GaussianMixture(nn.Module):
+    """flowtron.py:312-363: prob = softmax(prob_layer(e)) [B,C]; mean / log_var either learned heads viewed as [B,M,C] or -- with
+    fixed_gaussian -- buffers [1,M,C] that travel in the state_dict (mean: C distinct one-hot rows scaled by mean_scale, drawn with
+    np.random.choice at construction; log_var zeros).  The three heads are B-row GEMMs with fp32 operands in every mode."""
+
+    def __init__(self, n_hidden, n_components, n_mel_channels, fixed_gaussian, mean_scale):
+        super().__init__()
+        self.n_mel_channels = n_mel_channels
+        self.n_components = n_components
+        self.fixed_gaussian = fixed_gaussian
+        self.mean_scale = mean_scale
+        self.prob_layer = LinearNorm(n_hidden, n_components)
+        if not fixed_gaussian:
+            self.mean_layer = LinearNorm(n_hidden, n_mel_channels * n_components)
+            self.log_var_layer = LinearNorm(n_hidden, n_mel_channels * n_components)
+        else:
+            self.register_buffer("mean", self.generate_mean(n_mel_channels, n_components, mean_scale).float())
+            self.register_buffer("log_var", self.generate_log_var(n_mel_channels, n_components).float())
+
+    def generate_mean(self, n_dimensions, n_components, scale=3):
+        means = torch.eye(n_dimensions).float()
+        ids = np.random.choice(range(n_dimensions), n_components, replace=False)
+        means = means[ids] * scale
+        return means.transpose(0, 1)[None]
+
+    def generate_log_var(self, n_dimensions, n_components):
+        return torch.zeros(1, n_dimensions, n_components).float()
+
+    def generate_prob(self):
+        return torch.ones(1, 1).float()
+
+    def forward(self, outputs, bs):
+        def head(layer):
+            return ops.linear(outputs, layer.linear_layer.weight, layer.linear_layer.bias, mode=L.FT_F32)
+        prob = ops.SoftmaxRowsFn.apply(head(self.prob_layer))
+        if not self.fixed_gaussian:
+            mean = head(self.mean_layer).view(bs, self.n_mel_channels, self.n_components)
+            log_var = head(self.log_var_layer).view(bs, self.n_mel_channels, self.n_components)
+        else:
+            mean, log_var = self.mean, self.log_var
+        return mean, log_var, prob
 
 
 # --------------------------------------------------------------------------
@@ -665,9 +773,9 @@ class Flowtron(nn.Module):
         self.flows = nn.ModuleList()
         self.encoder = Encoder(norm_fn=norm_fn, encoder_embedding_dim=n_text_dim)
         self.dummy_speaker_embedding = dummy_speaker_embedding
-        if n_components > 1:
-            raise NotImplementedError("the Gaussian-mixture prior (n_components > 1) is outside the hot path "
-                                      "(config.json:60 uses 0); see DESIGN.md")
+        if n_components > 1:                    # flowtron.py:846-851, registered behind the encoder as there
+            self.mel_encoder = MelEncoder(mel_encoder_n_hidden, norm_fn=norm_fn)
+            self.gaussian_mixture = GaussianMixture(mel_encoder_n_hidden, n_components, n_mel_channels, fixed_gaussian, mean_scale)
         for i in range(n_flows):
             add_gate = bool(i == (n_flows - 1) and use_gate_layer)
             cls = AR_Step if i % 2 == 0 else AR_Back_Step
@@ -692,14 +800,15 @@ class Flowtron(nn.Module):
         enc = self.encoder._run(emb, lens)
         return torch.cat([enc, spk], 2), lens
 
-    def forward(self, mel, speaker_ids, text, in_lens, out_lens, attn_prior=None):
+    def forward(self, mel, speaker_ids, text, in_lens, out_lens, attn_prior=None, _mixture=True):
         """mel [B,M,T], speaker_ids [B], text [B,L] (sorted by in_lens desc), in_lens/out_lens [B],
-        attn_prior [B,T,L] | None -> the reference's 8-tuple (flowtron.py:898-899)."""
+        attn_prior [B,T,L] | None -> the reference's 8-tuple (flowtron.py:898-899).  _mixture=False (latents, alignments: callers
+        that do not return the mixture) skips the mel encoder of a model built with n_components > 1; elements 5-7 are then None."""
         L.require_cuda(mel, text, in_lens, out_lens, attn_prior)
         ops.weight_images_begin(self)                # (the weights this model's previous forward rounded: one launch at the first request)
         ops.bias_sums_begin(self._lstm_bias_pairs())  # (b_ih + b_hh of every LSTM: one multi-tensor add)
         try:
-            return self._forward(mel, speaker_ids, text, in_lens, out_lens, attn_prior)
+            return self._forward(mel, speaker_ids, text, in_lens, out_lens, attn_prior, _mixture)
         finally:
             ops.bias_sums_end()
             ops.weight_images_end(self)
@@ -716,7 +825,7 @@ class Flowtron(nn.Module):
                         groups.setdefault(key, []).append((p, getattr(m, "bias_hh" + name[len("bias_ih"):])))
         return list(groups.values())
 
-    def _forward(self, mel, speaker_ids, text, in_lens, out_lens, attn_prior=None):
+    def _forward(self, mel, speaker_ids, text, in_lens, out_lens, attn_prior=None, mixture=True):
         enc, in32 = self._encode(speaker_ids, text, in_lens)
         out32 = ops.lens32(out_lens)
         x = mel.permute(2, 0, 1).contiguous().float()
@@ -735,6 +844,10 @@ class Flowtron(nn.Module):
                 attns_logprob_list.append(logprob)
             return x, log_s_list, gate, attns_list, attns_logprob_list
 
+        mean = log_var = prob = None
+        if mixture and hasattr(self, "gaussian_mixture"):        # flowtron.py:877-881
+            mel_embedding = self.mel_encoder(mel, out32)
+            mean, log_var, prob = self.gaussian_mixture(mel_embedding, mel_embedding.size(0))
         x0 = x
         x, log_s_list, gate, attns_list, attns_logprob_list = run_flows(x0, enc)
         if not torch.is_grad_enabled() and ops.PERSIST_LAUNCHES:
@@ -747,7 +860,7 @@ class Flowtron(nn.Module):
             if not ops.check_persist_status(raise_on_failure=False):
                 enc, in32 = self._encode(speaker_ids, text, in_lens)          # (the encoder's persistent BiLSTM may be the one that failed)
                 x, log_s_list, gate, attns_list, attns_logprob_list = run_flows(x0, enc)
-        return x, log_s_list, gate, attns_list, attns_logprob_list, None, None, None
+        return x, log_s_list, gate, attns_list, attns_logprob_list, mean, log_var, prob
 
     def latents(self, mel, speaker_ids, text, in_lens, out_lens, attn_prior=None):
         """z of a batch of utterances for style transfer (inference_style_transfer.ipynb runs `model(...)[0]` utterance by utterance):
@@ -786,7 +899,7 @@ class Flowtron(nn.Module):
                 attn_prior = attn_prior.index_select(0, idx)
         with torch.no_grad():
             out = self(mel, speaker_ids, text, torch.tensor([il[b] for b in order], dtype=torch.long, device=dev),
-                       torch.tensor([ol[b] for b in order], dtype=torch.long, device=dev), attn_prior)
+                       torch.tensor([ol[b] for b in order], dtype=torch.long, device=dev), attn_prior, _mixture=False)
             inv_idx = None
             if order != list(range(B)):
                 inv = [0] * B
@@ -1025,8 +1138,6 @@ class FlowtronLoss(nn.Module):
     def __init__(self, sigma=1.0, gm_loss=False, gate_loss=True, use_ctc_loss=False, ctc_loss_weight=0.0,
                  blank_logprob=-1):
         super().__init__()
-        if gm_loss:
-            raise NotImplementedError("gm_loss (Gaussian-mixture prior) is outside the hot path")
         self.sigma = sigma
         self.gm_loss = gm_loss
         self.gate_loss = gate_loss
@@ -1040,6 +1151,14 @@ class FlowtronLoss(nn.Module):
         out32 = ops.lens32(out_lengths)
         use_gate = self.gate_loss > 0
         lps = list(attn_logprob_list) if self.use_ctc_loss else []
+        if self.gm_loss:
+            # flowtron.py:217-231: the mixture likelihood as one node (ops.MixtureNLLFn); gate and CTC on the per-term path below
+            mean, log_var, prob = model_output[5:8]
+            if mean is None or log_var is None or prob is None:
+                raise ValueError("gm_loss=True needs the mixture in the model's output (elements 5-7 of its tuple), which a model "
+                                 "built with n_components <= 1 does not produce: set n_components > 1, or gm_loss=False")
+            loss = ops.MixtureNLLFn.apply(z, mean, log_var, prob, out32, *log_s_list)
+            return (loss,) + self._gate_and_ctc(z, gate_pred, gate_target, attn_logprob_list, in_lengths, out_lengths, out32)
         if ops.FUSED_LOSS and len(log_s_list) <= 8 and len(lps) <= 8 and all(lp is not None for lp in lps):
             # one autograd node, ten launches forward + backward (ops.FlowtronLossFn); the per-term path below is its restatement
             loss, gate_loss, loss_ctc = ops.FlowtronLossFn.apply(z, gate_pred if use_gate else None, gate_target if use_gate else None,
@@ -1049,6 +1168,10 @@ class FlowtronLoss(nn.Module):
                 loss_ctc = torch.zeros_like(gate_loss)
             return loss, gate_loss, loss_ctc
         loss = ops.NLLFn.apply(z, out32, float(self.sigma), *log_s_list)
+        return (loss,) + self._gate_and_ctc(z, gate_pred, gate_target, attn_logprob_list, in_lengths, out_lengths, out32)
+
+    def _gate_and_ctc(self, z, gate_pred, gate_target, attn_logprob_list, in_lengths, out_lengths, out32):
+        """(gate_loss, loss_ctc) term by term (flowtron.py:237-274)"""
         gate_loss = torch.zeros(1, device=z.device)
         if self.gate_loss > 0:
             gate_loss = ops.GateBCEFn.apply(gate_pred, gate_target, out32)
@@ -1063,4 +1186,4 @@ class FlowtronLoss(nn.Module):
             # of one (F*B of 256 CUs busy).  mean over the F*B stacked samples == mean over flows of the per-flow batch means.
             F_ = len(lps)
             loss_ctc = self.attention_loss(torch.cat(lps, 0) if F_ > 1 else lps[0], in_lengths.repeat(F_), out_lengths.repeat(F_))
-        return loss, gate_loss, loss_ctc
+        return gate_loss, loss_ctc

@@ -2427,3 +2427,128 @@ def durations_to_rows(dur32, in32, n_frames, reverse=False):
     L.check(L.lib().ft_durations_to_rows(L.ptr(dur32), L.ptr(in32), L.ptr(rows), B, n_frames, Lt, int(bool(reverse)), L.stream()),
             "ft_durations_to_rows")
     return rows
+
+
+# --------------------------------------------------------------------------
+# Gaussian-mixture prior (flowtron.py:217-231, 312-363, 437-439; csrc/mixture.hip)
+# --------------------------------------------------------------------------
+class TimePoolFn(torch.autograd.Function):
+    """y[b] = sum_{t < lens[b]} x[t, b] / max(lens): the reference's torch.mean over the time axis of the zero-padded BiLSTM
+    output (flowtron.py:437-439) -- the divisor is the batch's LONGEST length, taken on the device.  x [T,B,W] -> [B,W]."""
+
+    @staticmethod
+    def forward(ctx, x, lens):
+        x = _c(x)
+        L.require_cuda(x, lens)
+        T, B, W = x.shape
+        y = torch.empty(B, W, device=x.device, dtype=torch.float32)
+        L.check(L.lib().ft_time_pool_fwd(L.ptr(x), L.ptr(lens), L.ptr(y), T, B, W, L.stream()), "ft_time_pool_fwd")
+        ctx.save_for_backward(lens)
+        ctx.T = T
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lens, = ctx.saved_tensors
+        dy = _c(dy)
+        B, W = dy.shape
+        dx = torch.empty(ctx.T, B, W, device=dy.device, dtype=torch.float32)
+        L.check(L.lib().ft_time_pool_bwd(L.ptr(dy), L.ptr(lens), L.ptr(dx), ctx.T, B, W, L.stream()), "ft_time_pool_bwd")
+        return dx, None
+
+
+class SoftmaxRowsFn(torch.autograd.Function):
+    """softmax over the components of each row: [B,C] -> [B,C], 2 <= C <= 64 (flowtron.py:352)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = _c(x)
+        L.require_cuda(x)
+        B, Cn = x.shape
+        y = torch.empty_like(x)
+        L.check(L.lib().ft_softmax_rows_fwd(L.ptr(x), L.ptr(y), B, Cn, L.stream()), "ft_softmax_rows_fwd")
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, = ctx.saved_tensors
+        dy = _c(dy)
+        B, Cn = y.shape
+        dx = torch.empty_like(y)
+        L.check(L.lib().ft_softmax_rows_bwd(L.ptr(y), L.ptr(dy), L.ptr(dx), B, Cn, L.stream()), "ft_softmax_rows_bwd")
+        return dx
+
+
+class MixtureNLLFn(torch.autograd.Function):
+    """[-sum m log sum_c prob_c N(z; mean_c, exp(log_var_c)) - sum_f sum m log_s_f] / (n_valid_frames * n_mel), the Gaussians
+    without their 2 pi term (flowtron.py:217-235).  z [T,B,M]; mean, log_var [1,M,C] (fixed) or [B,M,C]; prob [B,C]; log_s: strided
+    views [T,B,M] of the coupling outputs.  One node: gradients to z, every log_s and -- where asked for -- mean, log_var, prob."""
+
+    @staticmethod
+    def forward(ctx, z, mean, log_var, prob, lens, *log_s):
+        z, mean, log_var, prob = _c(z), _c(mean), _c(log_var), _c(prob)
+        L.require_cuda(z, mean, log_var, prob, lens, *log_s)
+        T, B, M = z.shape
+        Bm, Cn = mean.shape[0], mean.shape[2]
+        if tuple(mean.shape) != (Bm, M, Cn) or log_var.shape != mean.shape or tuple(prob.shape) != (B, Cn):
+            raise ValueError("mixture shapes: mean / log_var [1 or B, M, C] and prob [B, C] for z [T, B, M], got %s, %s, %s, %s"
+                             % (tuple(mean.shape), tuple(log_var.shape), tuple(prob.shape), tuple(z.shape)))
+        ld = M
+        for ls in log_s:
+            assert ls.shape == z.shape and ls.dtype == torch.float32 and ls.stride(2) == 1 and ls.stride(1) * B == ls.stride(0)
+        if log_s:
+            ld = int(log_s[0].stride(1))
+            assert all(int(ls.stride(1)) == ld for ls in log_s)
+        dev = z.device
+        acc = torch.empty(8, device=dev, dtype=torch.float32)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        nw = L.lib().ft_mixture_nll_work_floats(T, B, M, Cn)
+        work = torch.empty(max(nw, 1), device=dev, dtype=torch.float32)
+        L.check(L.lib().ft_mixture_nll_fwd(L.ptr(z), L.ptr(mean), L.ptr(log_var), L.ptr(prob), _ptr_array(log_s) if log_s else None,
+                                           len(log_s), ld, L.ptr(lens), L.ptr(acc), L.ptr(work), L.ptr(loss), T, B, M, Cn, Bm,
+                                           L.stream()), "ft_mixture_nll_fwd")
+        ctx.save_for_backward(z, mean, log_var, prob, lens, acc)
+        ctx.n_ls = len(log_s)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        z, mean, log_var, prob, lens, acc = ctx.saved_tensors
+        T, B, M = z.shape
+        Bm, Cn = mean.shape[0], mean.shape[2]
+        dev = z.device
+        g = _c(g.reshape(1).to(torch.float32))
+        need = ctx.needs_input_grad
+        dz = torch.empty_like(z)
+        dls = torch.empty_like(z) if ctx.n_ls else None
+        f32 = dict(device=dev, dtype=torch.float32)
+        dmean = torch.empty(B, M, Cn, **f32) if need[1] else None
+        dlv = torch.empty(B, M, Cn, **f32) if need[2] else None
+        dprob = torch.empty(B, Cn, **f32) if need[3] else None
+        work = None
+        if need[1] or need[2] or need[3]:
+            work = torch.empty(L.lib().ft_mixture_nll_work_floats(T, B, M, Cn), **f32)
+        L.check(L.lib().ft_mixture_nll_bwd(L.ptr(z), L.ptr(mean), L.ptr(log_var), L.ptr(prob), L.ptr(lens), L.ptr(acc), L.ptr(g),
+                                           L.ptr(dz), L.ptr(dls), L.ptr(dmean), L.ptr(dlv), L.ptr(dprob), L.ptr(work), T, B, M, Cn, Bm,
+                                           L.stream()), "ft_mixture_nll_bwd")
+        if Bm == 1 and B > 1:                    # shared Gaussians that ask for a gradient (the reference's are buffers): add the rows
+            dmean = None if dmean is None else dmean.sum(0, keepdim=True)
+            dlv = None if dlv is None else dlv.sum(0, keepdim=True)
+        return (dz, dmean, dlv, dprob, None) + (dls,) * ctx.n_ls
+
+
+def mixture_sample(mean, log_var, component, n_frames, sigma=1.0, rows=None, eps=None):
+    """-> fp32 [S, M, n_frames]: out[s,m,t] = mean[rows[s],m,component[s]] + sigma exp(log_var[..] / 2) eps[s,m,t].  mean / log_var
+    [Bm,M,C]; component int32 [S] on the device; rows int32 [S] | None (row 0, Bm = 1); eps [S,M,n_frames] | None with sigma 0."""
+    mean, log_var = _c(mean.float()), _c(log_var.float())
+    L.require_cuda(mean, log_var, component, rows, eps)
+    Bm, M, Cn = mean.shape
+    S = component.shape[0]
+    if eps is not None:
+        eps = _c(eps.float())
+        assert tuple(eps.shape) == (S, M, n_frames)
+    out = torch.empty(S, M, n_frames, device=mean.device, dtype=torch.float32)
+    L.check(L.lib().ft_mixture_sample(L.ptr(mean), L.ptr(log_var), L.ptr(rows), L.ptr(component), L.ptr(eps), L.ptr(out), S, M,
+                                      n_frames, Cn, Bm, float(sigma), L.stream()), "ft_mixture_sample")
+    return out

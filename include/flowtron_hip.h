@@ -793,6 +793,41 @@ int ft_radam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, c
  * ft_lstm_persist_*) poisons the global gradient norm on EVERY rank, and the guard of ft_radam_step drops that step everywhere. */
 int ft_poison_if_nonzero(const int32_t* status_dev, float* dst, void* stream);
 
+/* ---- Gaussian-mixture prior (flowtron.py:217-231, 312-363, 437-439; csrc/mixture.hip; functions added at ABI 15) --------
+ * All fp32, no float atomics: every reduction is two-stage and ordered, so two calls on the same inputs give identical bits.
+ * Mixture negative log-likelihood of z [T,B,M] under C components: mean, log_var [Bm,M,C] with Bm = 1 (fixed Gaussians, shared
+ * by the batch) or Bm = B, prob [B,C]; with valid = t < out_lens[b] (lengths clamped to 0 ..= T; padded frames are never read),
+ *   l[t,b,m] = log sum_c prob[b,c] exp(-(z - mean_c)^2 / (2 exp(log_var_c))) / sqrt(exp(log_var_c))      (no sigma, no 2 pi term)
+ *            = lse_c(log prob_c - log_var_c / 2 - (z - mean_c)^2 exp(-log_var_c) / 2), formed in the log domain,
+ *   *loss_out = -(sum_valid l + sum_f sum_valid log_s[f]) / (n_valid_frames M).
+ * log_s, n_ls (<= 8), ld_ls: as the fused Flowtron loss forward takes them.  acc: 8 floats the backward reads ([4] = 1 / (n M)).
+ * work: the float count the work query returns (scratch; forward and backward may share it).  Limits, checked on the host before
+ * any device call (FT_EINVAL): 2 <= C <= FT_MIXTURE_MAX_C, Bm in {1, B}, M <= 256, (3 M C + 2 C) floats within 62 KB of LDS.
+ * Backward (g: the incoming gradient, one device float): dz [T,B,M] and dls [T,B,M] (the gradient of EVERY log_s; may be NULL),
+ * zeros at padded frames; dmean, dlog_var [B,M,C] (per utterance also when Bm = 1: the caller adds the rows), dprob [B,C] -- any
+ * of the three may be NULL; work is needed when one is given. */
+#define FT_MIXTURE_MAX_C 64
+size_t ft_mixture_nll_work_floats(int T, int B, int M, int C);
+int ft_mixture_nll_fwd(const float* z, const float* mean, const float* log_var, const float* prob, const float* const* log_s,
+                       int n_ls, int64_t ld_ls, const int32_t* out_lens, float* acc, float* work, float* loss_out,
+                       int T, int B, int M, int C, int Bm, void* stream);
+int ft_mixture_nll_bwd(const float* z, const float* mean, const float* log_var, const float* prob, const int32_t* out_lens,
+                       const float* acc, const float* g, float* dz, float* dls, float* dmean, float* dlog_var, float* dprob,
+                       float* work, int T, int B, int M, int C, int Bm, void* stream);
+/* y[b,c] = sum_{t < lens[b]} x[t,b,c] / max_b lens[b] (x [T,B,W] contiguous; the reference's torch.mean over the time axis of a
+ * zero-padded BiLSTM output, flowtron.py:437-439: the divisor is the batch's LONGEST length, found on the device), and its adjoint
+ * dx[t,b,c] = dy[b,c] / max_b lens[b] at t < lens[b], 0 beyond. */
+int ft_time_pool_fwd(const float* x, const int32_t* lens, float* y, int T, int B, int W, void* stream);
+int ft_time_pool_bwd(const float* dy, const int32_t* lens, float* dx, int T, int B, int W, void* stream);
+/* softmax over the C (2 ..= FT_MIXTURE_MAX_C) entries of each of B rows, and dx = y (dy - sum_c y_c dy_c) */
+int ft_softmax_rows_fwd(const float* x, float* y, int B, int C, void* stream);
+int ft_softmax_rows_bwd(const float* y, const float* dy, float* dx, int B, int C, void* stream);
+/* out[s,m,t] = mean[row_s,m,k_s] + sigma exp(log_var[row_s,m,k_s] / 2) eps[s,m,t]: S samples [S,M,n_frames] of ONE component each
+ * (component: device int32 [S]; rows: device int32 [S] into the Bm rows of mean / log_var, NULL = row 0 with Bm = 1).  eps: the
+ * caller's N(0,1) draws (NULL with sigma = 0: the component means).  A row or component outside its range gives NaN, reads nothing. */
+int ft_mixture_sample(const float* mean, const float* log_var, const int32_t* rows, const int32_t* component, const float* eps,
+                      float* out, int S, int M, int n_frames, int C, int Bm, float sigma, void* stream);
+
 /* ---- fp16-operand twins (FT_F16): same signatures, semantics and workspace queries as the entries they are named after;
  * 16-bit images / fragments made by a twin must only be fed to twins. ---- */
 int ft_gemm_f16(const ft_gemm_args* a, void* stream);

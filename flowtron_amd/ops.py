@@ -2430,6 +2430,40 @@ def durations_to_rows(dur32, in32, n_frames, reverse=False):
 
 
 # --------------------------------------------------------------------------
+# mel-cepstral distortion along a dynamic-time-warping path (csrc/dtw.hip)
+# --------------------------------------------------------------------------
+def mel_cepstra(mel, lens32_, dct):
+    """mel [B,M,T] fp32 of ANY strides (read in place), device int32 frame counts or None, dct [K,M] fp32 contiguous ->
+    cepstra [B,T,K] fp32; rows at or behind lens stay 0."""
+    L.require_cuda(mel, lens32_, dct)
+    B, M, T = mel.shape
+    K = dct.shape[0]
+    cep = torch.zeros(B, T, K, device=mel.device, dtype=torch.float32)
+    sb, sm, st = mel.stride()
+    L.check(L.lib().ft_mel_cepstra(L.ptr(mel), sb, sm, st, L.ptr(lens32_), L.ptr(dct), L.ptr(cep), B, M, T, K, L.stream()),
+            "ft_mel_cepstra")
+    return cep
+
+
+def dtw_ragged(x, y, x32, y32, diagonal=False):
+    """Dynamic time warping of a ragged batch of pairs: x [B,Ta,K], y [B,Tb,K] fp32 of ANY strides (read in place), device int32
+    lengths -> (cost [B] fp32, path [B, Ta+Tb-1, 2] int32 with -1 behind path_len, path_len [B] int32)."""
+    L.require_cuda(x, y, x32, y32)
+    B, Ta, K = x.shape
+    Tb = y.shape[1]
+    dev = x.device
+    cost = torch.empty(B, device=dev, dtype=torch.float32)
+    path_len = torch.empty(B, device=dev, dtype=torch.int32)
+    path = torch.empty(B, Ta + Tb - 1, 2, device=dev, dtype=torch.int32)
+    nbytes = L.lib().ft_dtw_workspace_bytes(B, Ta, Tb, K)
+    work = torch.empty(max(nbytes // 8, 2), device=dev, dtype=torch.int64)
+    L.check(L.lib().ft_dtw_ragged(L.ptr(x), *x.stride(), L.ptr(y), *y.stride(), L.ptr(x32), L.ptr(y32), L.ptr(cost),
+                                  L.ptr(path_len), L.ptr(path), L.ptr(work), nbytes, B, Ta, Tb, K, int(bool(diagonal)), L.stream()),
+            "ft_dtw_ragged")
+    return cost, path, path_len
+
+
+# --------------------------------------------------------------------------
 # Gaussian-mixture prior (flowtron.py:217-231, 312-363, 437-439; csrc/mixture.hip)
 # --------------------------------------------------------------------------
 class TimePoolFn(torch.autograd.Function):

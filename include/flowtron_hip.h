@@ -691,6 +691,40 @@ int ft_mas_ragged(const float* logp, int64_t stride_b, int64_t stride_t, int64_t
 int ft_durations_to_rows(const int32_t* durations, const int32_t* in_lens, float* rows, int B, int N, int L, int reverse,
                          void* stream);
 
+/* ---- mel-cepstral distortion along a dynamic-time-warping path (csrc/dtw.hip; additive, not in the reference) ----------
+ * mel_cepstra: truncated cepstra of log-mel frames.  mel: fp32 with ELEMENT strides (utterance, mel channel, frame), so a
+ * [B][M][T] tensor or any view of one is read in place; lens [B] device int32, clamped inside the kernel to 1 ..= T, or NULL
+ * for T frames everywhere; dct [K][M] fp32, row k-1 the DCT-II basis sqrt(2/M) cos(pi k (m + 0.5) / M) that the caller
+ * builds in float64 and rounds once (c0 is left out); cep [B][T][K] fp32 contiguous:
+ *     cep[b][t][k-1] = sum_m mel[b][m][t] * dct[k-1][m]        m ascending, every product and every sum rounded on its own
+ * Frames at or behind lens[b] are not read and their outputs are not written.  One launch.
+ * dtw_ragged: one pair of feature sequences per utterance, one launch, one workgroup per pair.  x [B][Ta][K] and y [B][Tb][K]
+ * fp32 with ELEMENT strides (pair, frame, feature); x_lens / y_lens [B] device int32, clamped inside the kernel to 1 ..= Ta
+ * and 1 ..= Tb; nothing at or behind A = x_lens[b] and N = y_lens[b] is read.  Per pair, every operation an fp32 operation
+ * rounded once (nothing is contracted into a fused multiply-add, the square root is correctly rounded):
+ *     d[i][j] = sqrt(sum_k (x[i][k] - y[j][k])^2)              k ascending
+ *     C[0][0] = d[0][0];   i == 0: move 2, from (i, j-1);   j == 0: move 1, from (i-1, j)
+ *     else  best = C[i-1][j-1], move 0;  if C[i-1][j] < best: best, move 1;  if C[i][j-1] < best: best, move 2
+ *     C[i][j] = d[i][j] + best;   backtrack from (A-1, N-1) to (0, 0)
+ * so a float32 replay on the host gives the same bits.  The compares are strict: a tie keeps the earlier move (diagonal
+ * before up before left; x and y are therefore NOT interchangeable), and the border moves do not look at the costs, so the
+ * path is structurally valid whatever the features hold (NaN and inf too).
+ * cost [B] fp32 = C[A-1][N-1]; path_len [B] int32; path [B][Ta + Tb - 1][2] int32: the cells (i, j) in ascending order, -1
+ * behind path_len[b].  diagonal != 0: only the cells i == j, cost = the running sum of d[i][i] over ascending i, path_len A;
+ * a pair with A != N has no such path: path_len 0, cost +inf, path -1.
+ * work: the backpointers, two bits per cell, dtw_workspace_bytes bytes (host arithmetic only; 0 for a size < 1), 16-byte
+ * aligned; contents need not be initialised.  No atomics, no communication between workgroups.
+ * FT_EINVAL before any device call: a NULL pointer (but lens of mel_cepstra), B, M, T, Ta, Tb or K < 1, a negative stride,
+ * B > 65535 (mel_cepstra), work misaligned or work_bytes too small.  FT_EUNSUPPORTED: mel_cepstra with K > 32, K >= M or
+ * M > 128; dtw_ragged with Ta or Tb > 1024 (a thread per column of y, the rows of x in LDS) or K > 32. */
+int ft_mel_cepstra(const float* mel, int64_t stride_b, int64_t stride_m, int64_t stride_t, const int32_t* lens, const float* dct,
+                   float* cep, int B, int M, int T, int K, void* stream);
+size_t ft_dtw_workspace_bytes(int B, int Ta, int Tb, int K);
+int ft_dtw_ragged(const float* x, int64_t x_stride_b, int64_t x_stride_t, int64_t x_stride_k, const float* y, int64_t y_stride_b,
+                  int64_t y_stride_t, int64_t y_stride_k, const int32_t* x_lens, const int32_t* y_lens, float* cost,
+                  int32_t* path_len, int32_t* path, void* work, size_t work_bytes, int B, int Ta, int Tb, int K, int diagonal,
+                  void* stream);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

@@ -6,6 +6,7 @@ another length, in dB (additive: the reference has no metric of its own; csrc/dt
 
     cep = mel_cepstra(mel, lens, n_coeffs=13)                                         # [B, T, K] cepstra 1 .. K (no c0)
     cost, path, path_len = dtw(cep_a, cep_b, a_lens, b_lens)                          # the warp itself, on any features
+    rmse_cents, vuv_error, n_voiced = f0_distortion(f0_a, f0_b, path, path_len)       # pitch error along a path (pitch.f0)
 
 Everything runs on the device and refuses tensors on the host; lengths are lists or integer tensors, on the host or the
 device (read to the host once, as Flowtron.infer reads them)."""
@@ -24,6 +25,7 @@ from .model import lengths_arg
 MAX_FRAMES = 1024          # ft_dtw_ragged: one thread per frame of the second sequence, the first one's frames in LDS
 MAX_COEFFS = 32
 MAX_MELS = 128
+MAX_LAG = 1022             # ft_f0_yin_ragged (pitch.f0): the longest lag tau_max = ceil(sampling_rate / fmin)
 
 MCD_SCALE = 10.0 / math.log(10.0) * math.sqrt(2.0)
 
@@ -155,3 +157,36 @@ def mel_cepstral_distortion(mel_a, a_lens, mel_b, b_lens, n_coeffs=13, align=Tru
     cost, path, path_len = _dtw(_cepstra(mel_a, al, K), _cepstra(mel_b, bl, K), al, bl, not align)
     mcd = (MCD_SCALE * cost.double() / path_len.double()).float()
     return (mcd, path, path_len) if return_path else mcd
+
+
+def f0_distortion(f0_a, f0_b, path, path_len):
+    """F0 error of two pitch contours along a warping path, pair by pair, in one launch: f0_a [B, Ta] and f0_b [B, Tb] in Hz
+    with 0 = unvoiced (fp32 on the device, any strides: pitch.f0 of the two waveforms at the mel front end's hop), path
+    [B, P, 2] int32 and path_len [B] int32 on the device as dtw() or mel_cepstral_distortion(..., return_path=True) return
+    them; cells at or behind path_len[b] are not read.
+    -> (rmse_cents [B] fp32: sqrt of the mean of (1200 log2(f0_a[i] / f0_b[j]))^2 over the cells (i, j) where both frames are
+    voiced, float64 throughout and rounded to fp32 once, NaN where there is no such cell; vuv_error [B] fp32: the share of
+    the path's cells where exactly one frame is voiced; n_voiced [B] int32: the cells where both are).
+    The contours are those of THIS project's tracker on Griffin-Lim audio: the numbers compare runs of this model, not papers."""
+    for t, name in ((f0_a, "f0_a"), (f0_b, "f0_b")):
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise ValueError("%s must be a [B, T] tensor, got %s" % (name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+        if min(t.shape) < 1:
+            raise ValueError("%s must hold at least one utterance and one frame, got shape %s" % (name, tuple(t.shape)))
+        if t.dtype != torch.float32:
+            raise ValueError("%s must be float32, got %s" % (name, t.dtype))
+    B, Ta = f0_a.shape
+    Tb = f0_b.shape[1]
+    if f0_b.shape[0] != B:
+        raise ValueError("f0_a holds %d contours and f0_b %d: one pair per utterance" % (B, f0_b.shape[0]))
+    if not torch.is_tensor(path) or path.dim() != 3 or path.shape[0] != B or path.shape[1] < 1 or path.shape[2] != 2 or path.dtype != torch.int32:
+        raise ValueError("path must be a [%d, P, 2] int32 tensor, got %s" % (B, (tuple(path.shape), path.dtype) if torch.is_tensor(path) else type(path).__name__))
+    if not torch.is_tensor(path_len) or tuple(path_len.shape) != (B,) or path_len.dtype != torch.int32:
+        raise ValueError("path_len must be a [%d] int32 tensor, got %s" % (B, (tuple(path_len.shape), path_len.dtype) if torch.is_tensor(path_len) else type(path_len).__name__))
+    if path.shape[1] > Ta + Tb - 1:
+        raise ValueError("path has room for %d cells, a warp of %d x %d frames has at most %d: these contours are not the path's" % (path.shape[1], Ta, Tb, Ta + Tb - 1))
+    L.require_cuda(f0_a, f0_b, path, path_len)
+    n_both, n_mismatch, sum_sq = ops.f0_path_stats(f0_a.detach(), f0_b.detach(), path.contiguous(), path_len.contiguous())
+    rmse = torch.sqrt(sum_sq / n_both.double()).float()                     # 0 / 0 = NaN where no cell has both voiced
+    vuv = (n_mismatch.double() / path_len.double()).float()
+    return rmse, vuv, n_both

@@ -2464,6 +2464,37 @@ def dtw_ragged(x, y, x32, y32, diagonal=False):
 
 
 # --------------------------------------------------------------------------
+# F0 tracking (YIN) and F0 error along a warping path (csrc/pitch.hip)
+# --------------------------------------------------------------------------
+def f0_yin_ragged(audio, n32, sampling_rate, hop, W, tau_min, tau_max, threshold):
+    """audio [B,N] fp32 of ANY strides (read in place), device int32 sample counts -> (f0 [B,T] fp32 Hz, 0 = unvoiced,
+    aperiodicity [B,T] fp32), T = N // hop + 1, zeros behind an utterance's n // hop + 1 frames."""
+    L.require_cuda(audio, n32)
+    B, N = audio.shape
+    T = N // hop + 1
+    f0 = torch.empty(B, T, device=audio.device, dtype=torch.float32)
+    ap = torch.empty(B, T, device=audio.device, dtype=torch.float32)
+    L.check(L.lib().ft_f0_yin_ragged(L.ptr(audio), *audio.stride(), L.ptr(n32), L.ptr(f0), L.ptr(ap), B, N, float(sampling_rate),
+                                     hop, W, tau_min, tau_max, float(threshold), L.stream()), "ft_f0_yin_ragged")
+    return f0, ap
+
+
+def f0_path_stats(f0_a, f0_b, path, path_len):
+    """f0_a [B,Ta], f0_b [B,Tb] fp32 of ANY strides, path [B,P,2] int32 contiguous, path_len [B] int32 -> (n_both [B] int32,
+    n_mismatch [B] int32, sum_sq [B] float64: squared cents over the cells where both frames are voiced)."""
+    L.require_cuda(f0_a, f0_b, path, path_len)
+    B, Ta = f0_a.shape
+    Tb, P = f0_b.shape[1], path.shape[1]
+    dev = f0_a.device
+    n_both = torch.empty(B, device=dev, dtype=torch.int32)
+    n_mismatch = torch.empty(B, device=dev, dtype=torch.int32)
+    sum_sq = torch.empty(B, device=dev, dtype=torch.float64)
+    L.check(L.lib().ft_f0_path_stats(L.ptr(f0_a), *f0_a.stride(), L.ptr(f0_b), *f0_b.stride(), L.ptr(path), L.ptr(path_len),
+                                     L.ptr(n_both), L.ptr(n_mismatch), L.ptr(sum_sq), B, Ta, Tb, P, L.stream()), "ft_f0_path_stats")
+    return n_both, n_mismatch, sum_sq
+
+
+# --------------------------------------------------------------------------
 # Gaussian-mixture prior (flowtron.py:217-231, 312-363, 437-439; csrc/mixture.hip)
 # --------------------------------------------------------------------------
 class TimePoolFn(torch.autograd.Function):

@@ -725,6 +725,42 @@ int ft_dtw_ragged(const float* x, int64_t x_stride_b, int64_t x_stride_t, int64_
                   int32_t* path_len, int32_t* path, void* work, size_t work_bytes, int B, int Ta, int Tb, int K, int diagonal,
                   void* stream);
 
+/* ---- F0 tracking (YIN) and F0 error along a warping path (csrc/pitch.hip; additive, not in the reference; functions added
+ * at ABI 15) ----------
+ * f0_yin_ragged: one launch for a zero-padded batch.  audio: fp32 with ELEMENT strides (utterance, sample), so a [B][N]
+ * tensor or any view of one is read in place; n_samples [B] device int32, clamped inside the kernel to 1 ..= N; f0 and
+ * aperiodicity [B][T] fp32 contiguous, T = N / hop + 1.  Utterance b has T_b = n_samples[b] / hop + 1 frames; frame t reads
+ * x[t hop - W/2 + j] for 0 <= j < W + tau_max + 1, samples before 0 or at or behind n_samples[b] read as 0 and their memory
+ * is never touched; outputs at t >= T_b are 0.  Per frame, every operation an fp32 operation rounded once (nothing is
+ * contracted into a fused multiply-add, the divisions are correctly rounded), so a float32 replay on the host gives the same
+ * bits:
+ *     d(tau) = sum_{j < W} (x[j] - x[j + tau])^2               tau = 0 .. tau_max + 1; j ascending: difference, square, add
+ *     s(tau) = s(tau - 1) + d(tau), ascending from s(0) = 0
+ *     d'(0) = 1;  d'(tau) = (d(tau) * float(tau)) / s(tau) where s(tau) > 0, and 1 where it is not (digital silence)
+ *     tau = the lowest lag in tau_min ..= tau_max with d'(tau) < threshold; from there upwards while tau < tau_max and
+ *           d'(tau + 1) < d'(tau)
+ *     voiced (such a lag exists): a, b, c = d'(tau - 1), d'(tau), d'(tau + 1), den = (a + c) - 2 b,
+ *           shift = (0.5 (a - c)) / den when a >= b, c >= b and den > 0, else 0;
+ *           f0 = sampling_rate / (float(tau) + shift), aperiodicity = b
+ *     unvoiced: f0 = 0, aperiodicity = the least d' in tau_min ..= tau_max
+ * A frame whose window holds a non-finite sample gives f0 = 0 (its aperiodicity is unspecified); other frames are untouched.
+ * f0_path_stats: per pair b over the cells c < path_len[b] of path [B][P][2] (int32 (i, j), as dtw_ragged writes them):
+ * n_both [B] int32 = cells with f0_a[i] > 0 and f0_b[j] > 0, n_mismatch [B] int32 = cells where exactly one is, sum_sq [B]
+ * float64 = the sum over the former of (1200 log2(f0_a[i] / f0_b[j]))^2, float64 throughout.  f0_a [B][Ta], f0_b [B][Tb]
+ * fp32 with ELEMENT strides (pair, frame).  One launch, one workgroup per pair, a fixed order of summation: the same bits on
+ * every call.  path_len is clamped to 0 ..= P and every index to its tensor inside the kernel, so a bad path reads nothing
+ * out of bounds.  No atomics.
+ * FT_EINVAL before any device call: a NULL pointer, B, N, hop, W, Ta, Tb or P < 1, a negative stride, B > 65535 or
+ * sampling_rate <= 0 (f0_yin_ragged), tau_min < 2, tau_max < tau_min, a threshold outside (0, 1], P > Ta + Tb - 1 (a
+ * monotone path has no more cells: a longer one leaves the tensors).  FT_EUNSUPPORTED: f0_yin_ragged with W > 2048, odd W
+ * or tau_max > 1022. */
+int ft_f0_yin_ragged(const float* audio, int64_t stride_b, int64_t stride_n, const int32_t* n_samples, float* f0,
+                     float* aperiodicity, int B, int N, float sampling_rate, int hop, int W, int tau_min, int tau_max,
+                     float threshold, void* stream);
+int ft_f0_path_stats(const float* f0_a, int64_t a_stride_b, int64_t a_stride_t, const float* f0_b, int64_t b_stride_b,
+                     int64_t b_stride_t, const int32_t* path, const int32_t* path_len, int32_t* n_both, int32_t* n_mismatch,
+                     double* sum_sq, int B, int Ta, int Tb, int P, void* stream);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

@@ -99,12 +99,38 @@ def window_sumsquare(window, n_frames, hop_length=200, win_length=800, n_fft=800
     return x
 
 
-def griffin_lim(magnitudes, stft_fn, n_iters=30):
+def _check_momentum(momentum):
+    if isinstance(momentum, (bool, np.bool_)) or not isinstance(momentum, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(momentum) < 1.0:
+        raise ValueError("momentum must be a number in [0, 1), got %r" % (momentum,))
+    return float(momentum)
+
+
+def _momentum_step(mag_c, angles, prev, nf, momentum, first):
+    """The fast Griffin-Lim step on the transform's (magnitude, phase), in place on the phase: one ft_gl_momentum launch."""
+    B, nb, T = angles.shape
+    L.check(L.lib().ft_gl_momentum(L.ptr(mag_c), L.ptr(angles), L.ptr(prev[0]), L.ptr(prev[1]), L.ptr(nf), B, nb, T, momentum,
+                                   1 if first else 0, L.stream()), "ft_gl_momentum")
+
+
+def griffin_lim(magnitudes, stft_fn, n_iters=30, momentum=0.0, n_frames=None, angles=None):
     """audio_processing.py:59-75 on the device.  magnitudes [B, n_fft/2+1, T] (device tensor), stft_fn an STFT.
     The starting angles are drawn on the host exactly as the reference draws them (np.random.rand, so np.random.seed(s)
     gives the reference's starting point) and copied to the device once; then n_iters x (ft_stft_r8 for the phase +
     ft_istft_r8, or ft_stft_pow2 + ft_istft_pow2 off the 1024 setting) run without a host synchronisation.
+    momentum (not in the reference; 0 <= momentum < 1) > 0 is fast Griffin-Lim (Perraudin et al. 2013; the common Python audio
+    library runs it at 0.99): with c the transform of an iteration's signal, the next phase is that of c + momentum (c - c_prev)
+    (ft_gl_momentum, one more launch per iteration between the two, the two planes of c_prev allocated once); the first
+    iteration has no c_prev and is the plain one, so n_iters = 1 gives the same bits with and without it.
+    n_frames (host integers, one per utterance; not in the reference): the batch is ragged and goes through griffin_lim_ragged's
+    loop with this momentum (1 + 3 n_iters launches for the whole batch when momentum > 0), from `angles` when given;
+    griffin_lim_ragged itself keeps its signature and is that loop at momentum 0.
     Returns [B, hop * (T - 1)]."""
+    momentum = _check_momentum(momentum)
+    if n_frames is not None:
+        return _griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters, angles, momentum)
+    if angles is not None:
+        raise ValueError("griffin_lim takes starting angles only with n_frames (the dense call draws them as the reference does)")
     L.require_cuda(magnitudes)
     stft_fn._check_spectrum(magnitudes, magnitudes)
     T = magnitudes.shape[-1]
@@ -114,8 +140,12 @@ def griffin_lim(magnitudes, stft_fn, n_iters=30):
     angles = np.angle(np.exp(2j * np.pi * np.random.rand(*magnitudes.size())))
     angles = torch.from_numpy(angles.astype(np.float32)).to(magnitudes.device)
     signal = stft_fn.inverse(magnitudes, angles).squeeze(1)
-    for _ in range(n_iters):
-        _, angles = stft_fn.transform(signal)
+    prev = torch.empty((2,) + tuple(magnitudes.shape), device=magnitudes.device, dtype=torch.float32) \
+        if momentum > 0.0 and n_iters > 0 else None
+    for it in range(n_iters):
+        mag_c, angles = stft_fn.transform(signal)
+        if prev is not None:
+            _momentum_step(mag_c, angles, prev, None, momentum, it == 0)
         signal = stft_fn.inverse(magnitudes, angles).squeeze(1)
     return signal
 
@@ -166,7 +196,15 @@ def griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters=30, angles=None):
     the same starting angles, zeros behind.  angles=None draws np.random.rand(*magnitudes.size()) exactly as griffin_lim does
     (with every length = T the two start from the same point under one seed); otherwise a [B, n_fft/2+1, T] starting phase on
     the host or the device.  The lengths go to the device once; then 1 + 2 n_iters launches (ft_istft_*_ragged, and
-    ft_stft_*_ragged_phase storing the phase only) serve the whole batch without a host synchronisation."""
+    ft_stft_*_ragged_phase storing the phase only) serve the whole batch without a host synchronisation.
+    The fast iteration of a ragged batch is griffin_lim(..., momentum=, n_frames=, angles=): 1 + 3 n_iters launches (the
+    analysis launch stores the magnitude too and ft_gl_momentum follows it); cells behind an utterance's end are neither read
+    nor written, so the promise above holds there as well."""
+    return _griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters, angles, 0.0)
+
+
+def _griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters, angles, momentum):
+    """The body of griffin_lim_ragged, with griffin_lim's momentum."""
     L.require_cuda(magnitudes)
     stft_fn._check_spectrum(magnitudes, magnitudes)
     B, nb, T = magnitudes.shape
@@ -188,8 +226,11 @@ def griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters=30, angles=None):
     both = _lengths_to_device(lens + [hop * (n - 1) for n in lens], m.device)
     nf, ns = both[:B], both[B:]
     signal = stft_fn._inverse_ragged(m, angles, nf)
-    for _ in range(n_iters):
-        _, angles = stft_fn._transform_ragged(signal, ns, want_magnitude=False)
+    prev = torch.empty((2, B, nb, T), device=m.device, dtype=torch.float32) if momentum > 0.0 and n_iters > 0 else None
+    for it in range(n_iters):
+        mag_c, angles = stft_fn._transform_ragged(signal, ns, want_magnitude=prev is not None)
+        if prev is not None:
+            _momentum_step(mag_c, angles, prev, nf, momentum, it == 0)
         signal = stft_fn._inverse_ragged(m, angles, nf)
     return signal
 
@@ -338,6 +379,35 @@ def filterbank_csr(mel_basis: np.ndarray):
     return np.asarray(bin0, np.int32), np.asarray(ptr, np.int32), np.asarray(w, np.float32)
 
 
+def filterbank_bin_table(bin0, ptr, w, n_bins):
+    """The transpose of filterbank_csr's bands, per bin: (band int32 [n_bins, 2], weight fp32 [n_bins, 2]) = the bands whose
+    run holds the bin, lower band first, -1 / 0 where there is none.  Slaney triangles overlap at most pairwise; a bin in more
+    than two bands raises NotImplementedError (ft_mel_nnls holds two per bin)."""
+    band = np.full((n_bins, 2), -1, dtype=np.int32)
+    weight = np.zeros((n_bins, 2), dtype=np.float32)
+    count = np.zeros(n_bins, dtype=np.int64)
+    for j in range(len(bin0)):
+        for i in range(int(ptr[j + 1] - ptr[j])):
+            k = int(bin0[j]) + i
+            if count[k] == 2:
+                raise NotImplementedError("bin %d of the mel filterbank lies in more than two bands (band %d is the third); "
+                                          "the NNLS mel inversion takes filterbanks whose bands overlap at most pairwise" % (k, j))
+            band[k, count[k]] = j
+            weight[k, count[k]] = w[ptr[j] + i]
+            count[k] += 1
+    return band, weight
+
+
+MEL_INVERSIONS = ("pinv", "nnls")
+
+
+def _check_inversion(method, n_iters):
+    if method not in MEL_INVERSIONS:
+        raise ValueError("the mel inversion method must be one of %s, got %r" % (MEL_INVERSIONS, method))
+    if isinstance(n_iters, (bool, np.bool_)) or not isinstance(n_iters, (int, np.integer)) or n_iters < 0:
+        raise ValueError("the mel inversion takes a non-negative integer number of iterations, got %r" % (n_iters,))
+
+
 POW2_NFFT = (256, 512, 1024, 2048, 4096)      # the analysis sizes of csrc/stft_pow2.hip
 
 
@@ -477,6 +547,7 @@ class TacotronSTFT(torch.nn.Module):
         basis = slaney_mel_filterbank(sampling_rate, filter_length, n_mel_channels, mel_fmin, mel_fmax)
         self.register_buffer("mel_basis", torch.from_numpy(basis).float())
         bin0, ptr, w = filterbank_csr(basis)          # sparse form of the same matrix for the rFFT kernel (not in the state_dict)
+        self._fb_host = (bin0, ptr, w)                # kept on the host for the per-bin table of the NNLS inversion
         self.register_buffer("fb_bin0", torch.from_numpy(bin0), persistent=False)
         self.register_buffer("fb_ptr", torch.from_numpy(ptr), persistent=False)
         self.register_buffer("fb_w", torch.from_numpy(w), persistent=False)
@@ -540,17 +611,22 @@ class TacotronSTFT(torch.nn.Module):
                                         st.filter_length, st.hop_length, self.n_mel_channels, L.stream()), "ft_stft_mel")
         return mel
 
-    def mel_to_magnitude(self, mel):
-        """Addition, not in the reference: log-mel [B, n_mel, T] (or [n_mel, T]) -> linear magnitudes [B, n_fft/2+1, T]
-        (or [n_fft/2+1, T]) = relu(pinv(mel_basis) @ spectral_de_normalize(mel)), the product on ft_gemm in fp32 with the
-        ReLU epilogue, one batched call.  Frames after an utterance's end that hold zeros decode as magnitude 1, not
-        silence: a batch of different lengths goes to mel_to_magnitude_ragged."""
-        L.require_cuda(mel)
-        if mel.dim() not in (2, 3) or mel.shape[-2] != self.n_mel_channels:
-            raise ValueError("mel_to_magnitude needs [B, %d, T] or [%d, T], got %s"
-                             % (self.n_mel_channels, self.n_mel_channels, tuple(mel.shape)))
+    def _bin_table(self, device):
+        """filterbank_bin_table of this filterbank on `device`, built on the first NNLS inversion and kept."""
+        hit = getattr(self, "_bin_table_dev", None)
+        if hit is None or hit[0].device != device:
+            band, weight = filterbank_bin_table(*self._fb_host, self.mel_pinv.shape[0])
+            hit = self._bin_table_dev = (torch.from_numpy(band).to(device), torch.from_numpy(weight).to(device))
+        return hit
+
+    def _mel_to_magnitude(self, mel, method, n_iters, lens, what):
+        """The body of mel_to_magnitude(_ragged): lens None (dense) or B host integers."""
         if self.mel_pinv.device != mel.device:
             self.to(mel.device)
+        if method == "nnls":
+            if self.fb_w.numel() < 1:
+                raise NotImplementedError("%s: the mel filterbank is empty" % what)
+            table = self._bin_table(mel.device)
         x = self.spectral_de_normalize(mel.float()).contiguous()
         x3 = x if x.dim() == 3 else x[None]
         B, n_mel, T = x3.shape
@@ -558,15 +634,53 @@ class TacotronSTFT(torch.nn.Module):
         out = torch.empty(B, nb, T, device=mel.device, dtype=torch.float32)
         gemm_raw(self.mel_pinv, x3, out, nb, T, n_mel, n_mel, 1, T, 1, T, act=L.ACT_RELU, batch=B, bsA=0, bsB=n_mel * T,
                  bsC=nb * T, mode=L.FT_F32)
+        nf = None if lens is None else _lengths_to_device(lens, out.device)
+        if method == "nnls":                            # in place on the estimate; zeros behind every length
+            L.check(L.lib().ft_mel_nnls(L.ptr(x3), L.ptr(out), L.ptr(out), L.ptr(nf), L.ptr(self.fb_bin0), L.ptr(self.fb_ptr),
+                                        L.ptr(self.fb_w), L.ptr(table[0]), L.ptr(table[1]), B, n_mel, self.stft_fn.filter_length, T,
+                                        self.fb_w.numel(), int(n_iters), L.stream()), "ft_mel_nnls")
+        elif nf is not None:
+            out.masked_fill_(torch.arange(T, device=out.device)[None, None, :] >= nf[:, None, None], 0.0)
         return out if mel.dim() == 3 else out[0]
 
-    def mel_to_audio(self, mel, n_iters=30):
+    def mel_to_magnitude(self, mel, method="pinv", n_iters=100, lengths=None):
+        """Addition, not in the reference: log-mel [B, n_mel, T] (or [n_mel, T]) -> linear magnitudes [B, n_fft/2+1, T]
+        (or [n_fft/2+1, T]) = relu(pinv(mel_basis) @ spectral_de_normalize(mel)), the product on ft_gemm in fp32 with the
+        ReLU epilogue, one batched call.  Frames after an utterance's end that hold zeros decode as magnitude 1, not
+        silence: a batch of different lengths goes to mel_to_magnitude_ragged.
+        method="nnls": the ReLU clips what the pseudo-inverse made negative, and the result no longer maps back onto the mel;
+        one more launch (ft_mel_nnls, csrc/vocode.hip) takes it as the start of n_iters multiplicative updates of
+        min ||mel_basis m - exp(mel)||^2 over m >= 0, the mel inversion of the common Python audio library (n_fft 256 .. 4096, at
+        most 128 bands that overlap at most pairwise).  Bins that no band covers stay 0.
+        lengths (host integers, one per utterance): mel_to_magnitude_ragged's result with this method -- zeros behind every
+        utterance, with method="nnls" written by ft_mel_nnls itself, which does not read the frames behind an utterance's end;
+        mel_to_magnitude_ragged keeps its signature and is this call at method="pinv"."""
+        _check_inversion(method, n_iters)
+        if lengths is not None:
+            lens = self._check_ragged_mel(mel, lengths, "mel_to_magnitude")
+            return self._mel_to_magnitude(mel, method, n_iters, lens, "mel_to_magnitude")
+        L.require_cuda(mel)
+        if mel.dim() not in (2, 3) or mel.shape[-2] != self.n_mel_channels:
+            raise ValueError("mel_to_magnitude needs [B, %d, T] or [%d, T], got %s"
+                             % (self.n_mel_channels, self.n_mel_channels, tuple(mel.shape)))
+        return self._mel_to_magnitude(mel, method, n_iters, None, "mel_to_magnitude")
+
+    def mel_to_audio(self, mel, n_iters=30, momentum=0.0, inversion="pinv", inversion_iters=100, lengths=None, angles=None):
         """Addition, not in the reference: log-mel [B, n_mel, T] (a dense batch, e.g. Flowtron.infer's output) or [n_mel, T]
-        -> waveform [B, hop * (T - 1)] (or [hop * (T - 1)]) = griffin_lim(mel_to_magnitude(mel), self.stft_fn, n_iters).
-        Every utterance of a batch must fill all T frames (zeros decode as magnitude 1, not silence): a batch of different
-        lengths, such as Flowtron.infer(..., return_lengths=True) returns, goes to mel_to_audio_ragged."""
-        mag = self.mel_to_magnitude(mel)
-        y = griffin_lim(mag if mag.dim() == 3 else mag[None], self.stft_fn, n_iters)
+        -> waveform [B, hop * (T - 1)] (or [hop * (T - 1)]) = griffin_lim(mel_to_magnitude(mel, inversion, inversion_iters),
+        self.stft_fn, n_iters, momentum).  Every utterance of a batch must fill all T frames (zeros decode as magnitude 1, not
+        silence): a batch of different lengths, such as Flowtron.infer(..., return_lengths=True) returns, goes to
+        mel_to_audio_ragged, or here with lengths= (host integers) and optionally angles= (mel_to_audio_ragged's starting
+        phase): mel_to_audio_ragged's pass with these options, utterance b still bit for bit the same call on it alone.
+        mel_to_audio_ragged keeps its signature and is this call at the defaults."""
+        _check_inversion(inversion, inversion_iters)
+        momentum = _check_momentum(momentum)
+        if lengths is not None:
+            return self._mel_to_audio_ragged(mel, lengths, n_iters, angles, momentum, inversion, inversion_iters)
+        if angles is not None:
+            raise ValueError("mel_to_audio takes starting angles only with lengths (the dense call draws them as the reference does)")
+        mag = self.mel_to_magnitude(mel, inversion, inversion_iters)
+        y = griffin_lim(mag if mag.dim() == 3 else mag[None], self.stft_fn, n_iters, momentum)
         return y if mel.dim() == 3 else y[0]
 
     def _check_ragged_mel(self, mel, lengths, what):
@@ -578,20 +692,26 @@ class TacotronSTFT(torch.nn.Module):
 
     def mel_to_magnitude_ragged(self, mel, lengths):
         """mel_to_magnitude for a batch of different lengths: log-mel [B, n_mel, T], utterance b holds lengths[b] frames (host
-        integers) -> [B, n_fft/2+1, T] with mel_to_magnitude's values inside each utterance and zero behind it."""
+        integers) -> [B, n_fft/2+1, T] with mel_to_magnitude's values inside each utterance and zero behind it.  The NNLS
+        inversion of a ragged batch is mel_to_magnitude(mel, method="nnls", lengths=lengths)."""
         lens = self._check_ragged_mel(mel, lengths, "mel_to_magnitude_ragged")
-        mag = self.mel_to_magnitude(mel)
-        T = mag.shape[2]
-        behind = torch.arange(T, device=mag.device)[None, None, :] >= _lengths_to_device(lens, mag.device)[:, None, None]
-        return mag.masked_fill_(behind, 0.0)
+        return self._mel_to_magnitude(mel, "pinv", 100, lens, "mel_to_magnitude_ragged")
 
     def mel_to_audio_ragged(self, mel, lengths, n_iters=30, angles=None):
         """mel_to_audio for a batch of different lengths in one Griffin-Lim pass: log-mel [B, n_mel, T] and the frames each
         utterance holds (host integers: Flowtron.infer(..., in_lens=, out_lens=, return_lengths=True) returns both) -> waveform
         [B, hop * (T - 1)] = griffin_lim_ragged(mel_to_magnitude(mel), lengths, self.stft_fn, n_iters, angles): utterance b
-        occupies [: hop * (lengths[b] - 1)], zeros behind.  The frames behind an utterance's end are never read by the loop."""
+        occupies [: hop * (lengths[b] - 1)], zeros behind.  The frames behind an utterance's end are never read by the loop.
+        Momentum and the NNLS inversion for a ragged batch: mel_to_audio(mel, ..., lengths=lengths, angles=angles)."""
+        return self._mel_to_audio_ragged(mel, lengths, n_iters, angles, 0.0, "pinv", 100)
+
+    def _mel_to_audio_ragged(self, mel, lengths, n_iters, angles, momentum, inversion, inversion_iters):
         L.require_cuda(mel)
         self.stft_fn._require_device_path("TacotronSTFT.mel_to_audio_ragged")
         lens = self._check_ragged_mel(mel, lengths, "mel_to_audio_ragged")
         _check_reflect(lens, self.stft_fn, "mel_to_audio_ragged", "lengths")
-        return griffin_lim_ragged(self.mel_to_magnitude(mel), lens, self.stft_fn, n_iters, angles)
+        if inversion == "pinv":
+            mag = self.mel_to_magnitude(mel)
+        else:
+            mag = self._mel_to_magnitude(mel, inversion, inversion_iters, lens, "mel_to_audio_ragged")
+        return _griffin_lim_ragged(mag, lens, self.stft_fn, n_iters, angles, momentum)

@@ -761,6 +761,40 @@ int ft_f0_path_stats(const float* f0_a, int64_t a_stride_b, int64_t a_stride_t, 
                      int64_t b_stride_t, const int32_t* path, const int32_t* path_len, int32_t* n_both, int32_t* n_mismatch,
                      double* sum_sq, int B, int Ta, int Tb, int P, void* stream);
 
+/* ---- mel -> waveform: NNLS mel inversion and the fast Griffin-Lim momentum step (csrc/vocode.hip; additive, not in the
+ * reference; functions added at ABI 15) ----------
+ * mel_nnls: one launch; per frame t of utterance b, min ||W m - s||^2 over m >= 0 by n_iters (>= 0) Lee-Seung multiplicative
+ * updates.  s [B][n_mel][T] the linear mel, m0 [B][nb][T] the starting estimate, m [B][nb][T] the result (m may be m0), all
+ * fp32 contiguous, nb = n_fft / 2 + 1.  n_frames [B] device int32, clamped inside the kernel to 0 ..= T, or NULL for T frames
+ * everywhere: frames at or behind n_frames[b] are never read (neither s nor m0) and m holds 0 there.
+ * W [n_mel][nb] comes twice.  By band, as TacotronSTFT's CSR: band j covers the len_j = fb_ptr[j+1] - fb_ptr[j] consecutive bins
+ * from fb_bin0[j] with the weights fb_w[fb_ptr[j] ..], nnz = fb_ptr[n_mel] weights in all.  By bin: bin_band [nb][2] int32 the
+ * bands that cover bin k, lower band first, -1 = none (a covered bin has [0] >= 0), bin_w [nb][2] fp32 their weights; a bin may
+ * lie in at most two bands.  Per frame, every operation an fp32 operation rounded once (nothing is contracted into a fused
+ * multiply-add, the divisions are correctly rounded), so a float32 replay on the host gives the same bits:
+ *     band(x)[j] = sum_{i < len_j} fb_w[fb_ptr[j] + i] * x[fb_bin0[j] + i]        from 0, i ascending: product, then add
+ *     bin(y)[k]  = bin_w[k][0] * y[bin_band[k][0]]  ( + bin_w[k][1] * y[bin_band[k][1]] when bin_band[k][1] >= 0 )
+ *     start: p[l] = sum of m0[k] over k = l, l + 16, l + 32, ... ascending from 0 (l = 0 .. 15); mean = (p[0] + ... + p[15],
+ *            ascending from 0) / float(nb); low = 1e-3f * mean;  m[k] = (m0[k] < low ? low : m0[k]) on covered bins, 0 elsewhere
+ *     q = bin(s) once;   each iteration:  r = band(m);  d = bin(r);  m[k] = d[k] > 0 ? (m[k] * q[k]) / d[k] : 0 on covered bins,
+ *            then m[k] = 0 where m[k] < 1e-30f (so the rule does not lean on how denormals are treated)
+ * An all-zero frame gives zeros; n_iters = 0 returns the start.  Band ranges and band numbers are clamped to their arrays inside
+ * the kernel.  No atomics, no scratch, no communication between workgroups.
+ * gl_momentum: one elementwise launch over [B][n_bins][T] between the analysis and the synthesis launch of a Griffin-Lim
+ * iteration: with c = magnitude * (cos(phase), sin(phase)) (sincosf; the transform's own magnitude and phase),
+ *     first == 0:  t = c + alpha * (c - c_prev) per component (difference, product, add);  phase = atan2f(t.im, t.re)
+ *     first != 0:  phase stays as it is (it is not written)
+ *     always:      c_prev = c                  (prev_re, prev_im: two fp32 planes of the same shape, read only when first == 0)
+ * n_frames as above (or NULL): cells at or behind n_frames[b] are neither read nor written.
+ * FT_EINVAL before any device call: a NULL pointer (but n_frames), B, n_mel, T, nnz or n_bins < 1, n_iters < 0, B > 65535,
+ * n_bins * T beyond 2^31 - 257, alpha outside [0, 1).  FT_EUNSUPPORTED: mel_nnls with n_fft not a power of two in 256 .. 4096,
+ * n_mel > 128, or more weights than the workgroup's LDS holds beside one frame. */
+int ft_mel_nnls(const float* s, const float* m0, float* m, const int32_t* n_frames, const int32_t* fb_bin0, const int32_t* fb_ptr,
+                const float* fb_w, const int32_t* bin_band, const float* bin_w, int B, int n_mel, int n_fft, int T, int nnz,
+                int n_iters, void* stream);
+int ft_gl_momentum(const float* magnitude, float* phase, float* prev_re, float* prev_im, const int32_t* n_frames, int B, int n_bins,
+                   int T, float alpha, int first, void* stream);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

@@ -20,12 +20,11 @@ neighbouring batch row, or from one step off -- must each exceed the tolerance a
 import pytest
 import torch
 
+from lstm_replay import (ACT_EPS, C_ACC, SHARP, U32, _cap, bufs, bwd64, check_bwd, check_fwd, dt16, gather_rows, keep_capsys, on_valid, op16,
+                         ratio, replay_bwd, replay_fwd, sharp_muts, steps)
+
 pytestmark = pytest.mark.gpu
 H = 1024
-U32 = 2.0 ** -24
-C_ACC = 16
-ACT_EPS = 2.0 ** -20
-SHARP = 10.0
 
 
 @pytest.fixture(scope="module")
@@ -36,14 +35,6 @@ def env():
     if not ops.persist_usable(torch.device("cuda", 0)):
         pytest.skip("persistent kernels not usable on this device")
     return L, ops
-
-
-def dt16(fmt):
-    return torch.float16 if fmt == 2 else torch.bfloat16
-
-
-def op16(t, fmt):
-    return t.to(dt16(fmt)).double()
 
 
 def make(T, B, seed, lens=None, scale=0.5, Hd=H):
@@ -58,177 +49,9 @@ def make(T, B, seed, lens=None, scale=0.5, Hd=H):
     return gx, w, torch.as_tensor(lens, dtype=torch.int32).cuda()
 
 
-def steps(lens, T, reverse, off=1):
-    """valid mask [T, B] and, per (t, b), the time of the step `off` steps earlier in the row's own order (clamped) with its mask"""
-    t = torch.arange(T, device=lens.device)[:, None]
-    ln = lens.long()[None, :]
-    valid = t < ln
-    tp = t + off if reverse else t - off
-    has = valid & (tp >= 0) & (tp < ln)
-    return valid, tp.clamp(0, T - 1).expand(T, lens.numel()), has
-
-
-def gather_rows(x, tp, bidx, has=None):
-    """x[tp[t, b], bidx[b]]; where `has` is False: 0 (pad rows of saved gates / cell are never written: no NaN * 0)"""
-    r = x[tp, bidx[None, :].expand_as(tp)]
-    return r if has is None else torch.where(has[..., None], r, torch.zeros((), dtype=r.dtype, device=r.device))
-
-
-def on_valid(x, valid):
-    return torch.where(valid[..., None], x, torch.zeros((), dtype=x.dtype, device=x.device))
-
-
-def ratio(err, tol, mask):
-    r = (err / tol)[mask]
-    return float(r.max()) if r.numel() else 0.0
-
-
-def replay_fwd(gx, w, lens, y, g, c, fmt, reverse=False, mutate=None, gx_tol=None):
-    """max |kernel - replay| / tol of (gates, cell, y) over the valid (t, b); gx_tol: an extra per-element bound on gx (a gx the test
-    derives itself)"""
-    T, B, Hd = y.shape
-    valid, tp, has = steps(lens, T, reverse, 2 if mutate == "step" else 1)
-    bidx = torch.arange(B, device=y.device)
-    if mutate == "row":
-        bidx = (bidx + 1) % B
-        has = has & gather_rows(valid, tp, bidx)
-    h16 = op16(gather_rows(y, tp, bidx, has), fmt)
-    W = w.double() if mutate == "w" else op16(w, fmt)
-    z = gx.double() + h16 @ W.t()
-    S = gx.double().abs() + h16.abs() @ W.abs().t()
-    del h16
-    tol_z = C_ACC * U32 * S
-    if gx_tol is not None:
-        tol_z = tol_z + gx_tol
-    del S
-    zi, zf, zg, zo = z.chunk(4, -1)
-    ref = torch.cat([torch.sigmoid(zi), torch.sigmoid(zf), torch.tanh(zg), torch.sigmoid(zo)], -1)
-    del z, zi, zf, zg, zo
-    slope = ref * (1 - ref)
-    slope[..., 2 * Hd:3 * Hd] = 1 - ref[..., 2 * Hd:3 * Hd] ** 2
-    r_g = ratio((g.double() - ref).abs(), slope * tol_z + ACT_EPS, valid[..., None].expand_as(ref))
-    del ref, slope, tol_z
-    if mutate is not None:
-        return r_g, None, None
-    _, tp1, has1 = steps(lens, T, reverse, 1)
-    gi, gf, gg, go = on_valid(g.double(), valid).chunk(4, -1)
-    c_prev = gather_rows(c, tp1, torch.arange(B, device=y.device), has1).double()
-    c_ref = gf * c_prev + gi * gg
-    r_c = ratio((c.double() - c_ref).abs(), 2 * U32 * ((gi * gg).abs() + c_ref.abs()) + 1e-38, valid[..., None].expand_as(c_ref))
-    y_ref = go * torch.tanh(on_valid(c.double(), valid))
-    r_y = ratio((y.double() - y_ref).abs(), go.abs() * ACT_EPS + 2 * U32 * y_ref.abs() + 1e-38, valid[..., None].expand_as(y_ref))
-    assert float(y[~valid].abs().max()) == 0.0 if bool((~valid).any()) else True, "pad rows of y must be exactly 0"
-    return r_g, r_c, r_y
-
-
-def replay_bwd(dy, w, lens, g, c, dgx, fmt, reverse=False, mutate=None):
-    """max |dgx - replay| / tol over the valid (t, b): dh from the kernel's own dgx of the row's next step, dc as a float64 scan
-    carried together with its error bound
-        E_t = |fA| e_dh + 2 |dh o tc| ACT_EPS + u (3 |dh fA| + 2 |f_next dc_next| + |dc_t|) + f_next E_next,   fA = o (1 - tc^2)
-    (the kernel: fA from the saved gates and a fast tanh, dc = fma(dh, fA, carry), carry = dc f)"""
-    T, B, Hd = c.shape
-    valid, tn, has = steps(lens, T, not reverse, 2 if mutate == "step" else 1)       # (the NEXT step: the previous one of the reversed order)
-    bidx = torch.arange(B, device=dy.device)
-    if mutate == "row":
-        bidx = (bidx + 1) % B
-        has = has & gather_rows(valid, tn, bidx)
-    d16 = op16(gather_rows(dgx, tn, bidx, has), fmt)
-    W = w.double() if mutate == "w" else op16(w, fmt)
-    dyd = dy[..., :Hd].double()
-    dh = dyd + d16 @ W
-    e_dh = C_ACC * U32 * (dyd.abs() + d16.abs() @ W.abs())
-    del d16
-    _, tp1, hasp = steps(lens, T, reverse, 1)
-    _, tn1, hasn = steps(lens, T, not reverse, 1)
-    b0 = torch.arange(B, device=dy.device)
-    gd = on_valid(g.double(), valid)
-    gi, gf, gg, go = gd.chunk(4, -1)
-    cd = on_valid(c.double(), valid)
-    c_prev = gather_rows(cd, tp1, b0, hasp)
-    tc = torch.tanh(cd)
-    fA = go * (1 - tc * tc)
-    f_next = gather_rows(gf, tn1, b0, hasn)
-    dc = torch.zeros_like(cd)
-    E = torch.zeros_like(cd)
-    order = range(T) if reverse else reversed(range(T))
-    vm = valid[..., None].double()
-    for t in order:
-        # the next step of row b in its own order: t + 1 (forward) / t - 1 (reverse); its dc sits there once computed
-        tn_b = tn1[t]
-        m = hasn[t][:, None].double()
-        carry_t = dc[tn_b, b0] * m
-        e_t = E[tn_b, b0] * m
-        a, b = dh[t] * fA[t], f_next[t] * carry_t
-        dct = (a + b) * vm[t]
-        dc[t] = dct
-        E[t] = (fA[t].abs() * e_dh[t] + 2 * (dh[t] * go[t] * tc[t]).abs() * ACT_EPS + U32 * (3 * a.abs() + 2 * b.abs() + dct.abs())
-                + f_next[t].abs() * e_t) * vm[t]
-    ref = torch.cat([dc * gg * gi * (1 - gi), dc * c_prev * gf * (1 - gf), dc * gi * (1 - gg * gg), dh * tc * go * (1 - go)], -1)
-    tol = torch.cat([(gg * gi * (1 - gi)).abs() * E, (c_prev * gf * (1 - gf)).abs() * E, (gi * (1 - gg * gg)).abs() * E,
-                     (tc * go * (1 - go)).abs() * e_dh + (dh * go * (1 - go)).abs() * ACT_EPS], -1) + 4 * U32 * ref.abs() + 1e-38
-    r = ratio((dgx.double() - ref).abs(), tol, valid[..., None].expand_as(ref))
-    if mutate is None:
-        pad = ~valid
-        if bool(pad.any()):
-            assert float(dgx[pad].abs().max()) == 0.0, "pad rows of dgx must be exactly 0"
-    return r
-
-
-def sharp_muts(lens, B):
-    if int(lens.max()) < 2:
-        return []                                        # (T = 1: no recurrent term to mutate)
-    out = ["w"]
-    if B > 1:
-        out.append("row")
-    if int(lens.max()) >= 3:
-        out.append("step")
-    return out
-
-
-def check_fwd(name, gx, w, lens, y, g, c, fmt, reverse=False, gx_tol=None, sharp=True):
-    rg, rc, ry = replay_fwd(gx, w, lens, y, g, c, fmt, reverse, gx_tol=gx_tol)
-    muts = {m: replay_fwd(gx, w, lens, y, g, c, fmt, reverse, m, gx_tol=gx_tol)[0] for m in (sharp_muts(lens, y.shape[1]) if sharp else [])}
-    with _cap():
-        print("\n[replay fwd] %-44s gates %.3f  cell %.3f  y %.3f  of tol;  mutations %s" % (name, rg, rc, ry, {k: round(v, 1) for k, v in muts.items()}))
-    assert rg <= 1.0 and rc <= 1.0 and ry <= 1.0, (name, rg, rc, ry)
-    for m, v in muts.items():
-        assert v >= SHARP, ("mutation %s not caught" % m, name, v)
-
-
-def check_bwd(name, dy, w, lens, g, c, dgx, fmt, reverse=False, sharp=True):
-    r = replay_bwd(dy, w, lens, g, c, dgx, fmt, reverse)
-    muts = {m: replay_bwd(dy, w, lens, g, c, dgx, fmt, reverse, m) for m in (sharp_muts(lens, dy.shape[1]) if sharp else [])}
-    with _cap():
-        print("\n[replay bwd] %-44s dgates %.3f of tol;  mutations %s" % (name, r, {k: round(v, 1) for k, v in muts.items()}))
-    assert r <= 1.0, (name, r)
-    for m, v in muts.items():
-        assert v >= SHARP, ("mutation %s not caught" % m, name, v)
-
-
-_CAPSYS = {}
-
-
-class _cap:
-    def __enter__(self):
-        c = _CAPSYS.get("c")
-        self.cm = c.disabled() if c is not None else None
-        if self.cm is not None:
-            self.cm.__enter__()
-
-    def __exit__(self, *a):
-        if self.cm is not None:
-            self.cm.__exit__(*a)
-
-
 @pytest.fixture(autouse=True)
 def _keep_capsys(capsys):
-    _CAPSYS["c"] = capsys
-    yield
-    _CAPSYS.pop("c", None)
-
-
-def bufs(T, B):
-    return torch.full((T, B, H), 7.0, device="cuda"), torch.full((T, B, 4 * H), 7.0, device="cuda"), torch.full((T, B, H), 7.0, device="cuda")
+    yield from keep_capsys(capsys)
 
 
 def clean(ops):
@@ -576,33 +399,6 @@ def test_decoder_pair_forward_replays_both_layers(env, nch, g16):
         ins[0] = ins[0].to(dt16(fmt))
     y1 = pair_forward(ops, fmt, *ins, nch)
     check_pair_forward("pair fwd nch %d gx16 %d" % (nch, g16), ops, fmt, *ins, y1)
-
-
-def bwd64(dy, w, lens, g, c, fmt, round_w=True):
-    """float64 backward recurrence with the kernels' operand roundings (op16 of W_hh and of each step's dgates in the recurrent
-    product), step by step in the row's order: dgates [T, B, 4H]"""
-    T, B = dy.shape[:2]
-    W = op16(w, fmt) if round_w else w.double()
-    vb = torch.arange(T, device=dy.device)[:, None] < lens.long()[None, :]
-    gd, cd = on_valid(g.double(), vb), on_valid(c.double(), vb)
-    gi, gf, gg, go = gd.chunk(4, -1)
-    valid = vb.double()[..., None]
-    tc = torch.tanh(cd)
-    da = torch.zeros(T, B, 4 * H, dtype=torch.float64, device=dy.device)
-    dc_next = torch.zeros(B, H, dtype=torch.float64, device=dy.device)
-    f_next = torch.zeros_like(dc_next)
-    rec = torch.zeros_like(dc_next)
-    for t in reversed(range(T)):
-        v = valid[t]
-        dh = (dy[t].double() + rec) * v
-        dc = (dh * go[t] * (1 - tc[t] ** 2) + f_next * dc_next) * v
-        c_prev = cd[t - 1] if t > 0 else torch.zeros_like(dc)
-        a = torch.cat([dc * gg[t] * gi[t] * (1 - gi[t]), dc * c_prev * gf[t] * (1 - gf[t]), dc * gi[t] * (1 - gg[t] ** 2),
-                       dh * tc[t] * go[t] * (1 - go[t])], -1) * v
-        da[t] = a
-        rec = op16(a, fmt) @ W
-        dc_next, f_next = dc, gf[t] * v
-    return da
 
 
 def pair_reference_grads(fmt, w_hh0, w_ih1, w_hh1, lens, y0, g0, c0, y1, g1, c1, dy1, round_w=True):

@@ -12,7 +12,8 @@ the inverse real FFT + overlap-add kernel of the setting's family, `griffin_lim`
 kernel on the device, and `window_sumsquare` is the reference's host function.  TacotronSTFT.mel_to_magnitude /
 mel_to_audio (not in the reference) turn model output into a waveform; the `_ragged` forms (STFT.transform_ragged /
 inverse_ragged, `griffin_lim_ragged`, mel_to_magnitude_ragged / mel_to_audio_ragged) do the same for a batch of utterances of
-different lengths in one launch per step.
+different lengths in one launch per step.  `spsi_phase` (ft_spsi_phase, not in the reference either) is the single-pass
+phase start that griffin_lim / mel_to_audio take with phase_init="spsi".
 
 The mel filterbank constants come from librosa in the reference (third-party dependency that is
 not vendored: requirements.txt:4 pins 0.6.3, Dockerfile:6 pins 0.8.0; call site
@@ -113,7 +114,52 @@ def _momentum_step(mag_c, angles, prev, nf, momentum, first):
                                    1 if first else 0, L.stream()), "ft_gl_momentum")
 
 
-def griffin_lim(magnitudes, stft_fn, n_iters=30, momentum=0.0, n_frames=None, angles=None):
+PHASE_INITS = ("random", "spsi")
+
+
+def _check_phase_init(phase_init, angles):
+    if not isinstance(phase_init, str) or phase_init not in PHASE_INITS:
+        raise ValueError("phase_init must be one of %s, got %r" % (PHASE_INITS, phase_init))
+    if phase_init != "random" and angles is not None:
+        raise ValueError("phase_init=%r computes the starting angles itself: it is refused together with angles=" % phase_init)
+    return phase_init
+
+
+def _spsi_launch(m, nf, stft_fn):
+    """m [B, n_fft/2+1, T] contiguous fp32 on the device, nf [B] int32 on the device or None -> angles of m's shape: one
+    ft_spsi_phase launch."""
+    B, _, T = m.shape
+    angles = torch.empty_like(m)
+    L.check(L.lib().ft_spsi_phase(L.ptr(m), L.ptr(angles), L.ptr(nf), B, stft_fn.filter_length, stft_fn.hop_length, T, L.stream()),
+            "ft_spsi_phase")
+    return angles
+
+
+def spsi_phase(magnitudes, stft_fn, n_frames=None):
+    """Single Pass Spectrogram Inversion (Beauregard, Harish, Wyse 2015; not in the reference): a starting phase for Griffin-Lim
+    from the magnitudes alone, in one launch (ft_spsi_phase, csrc/vocode.hip; the rule is in include/flowtron_hip.h).  Every
+    frame's spectral peaks get an instantaneous frequency by quadratic interpolation, a per-bin accumulator advances by
+    hop x frequency from frame to frame, and the bins of a peak's lobe are locked to the peak's phase.
+    magnitudes [B, n_fft/2+1, T] or [n_fft/2+1, T] float32 on the device, stft_fn an STFT with a device path; n_frames (host
+    integers in 0 ..= T, one per utterance): the batch is ragged, the angles at and behind an utterance's end are 0 and the
+    magnitudes there are never read.  Returns float32 angles of the magnitudes' shape in [-pi, pi]."""
+    stft_fn._require_device_path("spsi_phase")
+    nb = stft_fn.filter_length // 2 + 1
+    if not torch.is_tensor(magnitudes) or magnitudes.dim() not in (2, 3) or magnitudes.shape[-2] != nb or magnitudes.shape[-1] < 1:
+        raise ValueError("spsi_phase needs magnitudes of shape [B, %d, T] or [%d, T] with T >= 1, got %s"
+                         % (nb, nb, tuple(magnitudes.shape) if torch.is_tensor(magnitudes) else type(magnitudes).__name__))
+    if magnitudes.dtype != torch.float32:
+        raise ValueError("spsi_phase needs float32 magnitudes, got %s" % magnitudes.dtype)
+    m = magnitudes if magnitudes.dim() == 3 else magnitudes[None]
+    B, _, T = m.shape
+    lens = None if n_frames is None else _host_lengths(n_frames, B, 0, T, "n_frames", "0 ..= T = %d" % T)
+    L.require_cuda(magnitudes)
+    m = m.contiguous()
+    angles = _spsi_launch(m, None if lens is None else _lengths_to_device(lens, m.device), stft_fn)
+    return angles if magnitudes.dim() == 3 else angles[0]
+
+
+def griffin_lim(magnitudes, stft_fn, n_iters=30, momentum=0.0, n_frames=None, angles=None, phase_init="random"):
     """audio_processing.py:59-75 on the device.  magnitudes [B, n_fft/2+1, T] (device tensor), stft_fn an STFT.
     The starting angles are drawn on the host exactly as the reference draws them (np.random.rand, so np.random.seed(s)
     gives the reference's starting point) and copied to the device once; then n_iters x (ft_stft_r8 for the phase +
@@ -125,10 +171,14 @@ def griffin_lim(magnitudes, stft_fn, n_iters=30, momentum=0.0, n_frames=None, an
     n_frames (host integers, one per utterance; not in the reference): the batch is ragged and goes through griffin_lim_ragged's
     loop with this momentum (1 + 3 n_iters launches for the whole batch when momentum > 0), from `angles` when given;
     griffin_lim_ragged itself keeps its signature and is that loop at momentum 0.
+    phase_init (not in the reference): "random" is the draw above; "spsi" starts from spsi_phase(magnitudes) instead (one more
+    launch, no draw, refused together with angles=) and runs the ragged loop, a dense batch with every length T.  From that
+    start a few iterations do what some thirty do from the random one, and n_iters = 0 is the single-pass inversion.
     Returns [B, hop * (T - 1)]."""
     momentum = _check_momentum(momentum)
-    if n_frames is not None:
-        return _griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters, angles, momentum)
+    phase_init = _check_phase_init(phase_init, angles)
+    if n_frames is not None or phase_init != "random":
+        return _griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters, angles, momentum, phase_init)
     if angles is not None:
         raise ValueError("griffin_lim takes starting angles only with n_frames (the dense call draws them as the reference does)")
     L.require_cuda(magnitudes)
@@ -203,15 +253,17 @@ def griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters=30, angles=None):
     return _griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters, angles, 0.0)
 
 
-def _griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters, angles, momentum):
-    """The body of griffin_lim_ragged, with griffin_lim's momentum."""
+def _griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters, angles, momentum, phase_init="random"):
+    """The body of griffin_lim_ragged, with griffin_lim's momentum and phase_init (n_frames None: every utterance T frames)."""
     L.require_cuda(magnitudes)
     stft_fn._check_spectrum(magnitudes, magnitudes)
     B, nb, T = magnitudes.shape
     hop = stft_fn.hop_length
-    lens = _host_lengths(n_frames, B, 1, T, "n_frames", "1 ..= T = %d" % T)
+    lens = [T] * B if n_frames is None else _host_lengths(n_frames, B, 1, T, "n_frames", "1 ..= T = %d" % T)
     _check_reflect(lens, stft_fn, "griffin_lim_ragged", "n_frames")
-    if angles is None:
+    if phase_init == "spsi":
+        pass                                            # from the magnitudes, once they and the lengths are on the device
+    elif angles is None:
         angles = np.angle(np.exp(2j * np.pi * np.random.rand(*magnitudes.size())))
         angles = torch.from_numpy(angles.astype(np.float32))
     else:
@@ -219,12 +271,15 @@ def _griffin_lim_ragged(magnitudes, n_frames, stft_fn, n_iters, angles, momentum
         if tuple(angles.shape) != (B, nb, T):
             raise ValueError("griffin_lim_ragged needs angles of the magnitudes' shape %s, got %s"
                              % ((B, nb, T), tuple(angles.shape)))
-    angles = angles.to(magnitudes.device, torch.float32).contiguous()
     m = magnitudes.contiguous().float()
     if stft_fn.fft_window.device != m.device:
         stft_fn.to(m.device)
     both = _lengths_to_device(lens + [hop * (n - 1) for n in lens], m.device)
     nf, ns = both[:B], both[B:]
+    if phase_init == "spsi":
+        angles = _spsi_launch(m, nf, stft_fn)
+    else:
+        angles = angles.to(magnitudes.device, torch.float32).contiguous()
     signal = stft_fn._inverse_ragged(m, angles, nf)
     prev = torch.empty((2, B, nb, T), device=m.device, dtype=torch.float32) if momentum > 0.0 and n_iters > 0 else None
     for it in range(n_iters):
@@ -665,22 +720,27 @@ class TacotronSTFT(torch.nn.Module):
                              % (self.n_mel_channels, self.n_mel_channels, tuple(mel.shape)))
         return self._mel_to_magnitude(mel, method, n_iters, None, "mel_to_magnitude")
 
-    def mel_to_audio(self, mel, n_iters=30, momentum=0.0, inversion="pinv", inversion_iters=100, lengths=None, angles=None):
+    def mel_to_audio(self, mel, n_iters=30, momentum=0.0, inversion="pinv", inversion_iters=100, lengths=None, angles=None,
+                     phase_init="random"):
         """Addition, not in the reference: log-mel [B, n_mel, T] (a dense batch, e.g. Flowtron.infer's output) or [n_mel, T]
         -> waveform [B, hop * (T - 1)] (or [hop * (T - 1)]) = griffin_lim(mel_to_magnitude(mel, inversion, inversion_iters),
         self.stft_fn, n_iters, momentum).  Every utterance of a batch must fill all T frames (zeros decode as magnitude 1, not
         silence): a batch of different lengths, such as Flowtron.infer(..., return_lengths=True) returns, goes to
         mel_to_audio_ragged, or here with lengths= (host integers) and optionally angles= (mel_to_audio_ragged's starting
         phase): mel_to_audio_ragged's pass with these options, utterance b still bit for bit the same call on it alone.
-        mel_to_audio_ragged keeps its signature and is this call at the defaults."""
+        mel_to_audio_ragged keeps its signature and is this call at the defaults.
+        phase_init="spsi": Griffin-Lim starts from spsi_phase of the inverted magnitudes instead of the random draw (griffin_lim's
+        phase_init; refused together with angles=); with n_iters=0 the whole vocode is three launches after the pseudo-inverse:
+        NNLS, ft_spsi_phase and one inverse STFT."""
         _check_inversion(inversion, inversion_iters)
         momentum = _check_momentum(momentum)
+        phase_init = _check_phase_init(phase_init, angles)
         if lengths is not None:
-            return self._mel_to_audio_ragged(mel, lengths, n_iters, angles, momentum, inversion, inversion_iters)
+            return self._mel_to_audio_ragged(mel, lengths, n_iters, angles, momentum, inversion, inversion_iters, phase_init)
         if angles is not None:
             raise ValueError("mel_to_audio takes starting angles only with lengths (the dense call draws them as the reference does)")
         mag = self.mel_to_magnitude(mel, inversion, inversion_iters)
-        y = griffin_lim(mag if mag.dim() == 3 else mag[None], self.stft_fn, n_iters, momentum)
+        y = griffin_lim(mag if mag.dim() == 3 else mag[None], self.stft_fn, n_iters, momentum, phase_init=phase_init)
         return y if mel.dim() == 3 else y[0]
 
     def _check_ragged_mel(self, mel, lengths, what):
@@ -705,7 +765,7 @@ class TacotronSTFT(torch.nn.Module):
         Momentum and the NNLS inversion for a ragged batch: mel_to_audio(mel, ..., lengths=lengths, angles=angles)."""
         return self._mel_to_audio_ragged(mel, lengths, n_iters, angles, 0.0, "pinv", 100)
 
-    def _mel_to_audio_ragged(self, mel, lengths, n_iters, angles, momentum, inversion, inversion_iters):
+    def _mel_to_audio_ragged(self, mel, lengths, n_iters, angles, momentum, inversion, inversion_iters, phase_init="random"):
         L.require_cuda(mel)
         self.stft_fn._require_device_path("TacotronSTFT.mel_to_audio_ragged")
         lens = self._check_ragged_mel(mel, lengths, "mel_to_audio_ragged")
@@ -714,4 +774,4 @@ class TacotronSTFT(torch.nn.Module):
             mag = self.mel_to_magnitude(mel)
         else:
             mag = self._mel_to_magnitude(mel, inversion, inversion_iters, lens, "mel_to_audio_ragged")
-        return _griffin_lim_ragged(mag, lens, self.stft_fn, n_iters, angles, momentum)
+        return _griffin_lim_ragged(mag, lens, self.stft_fn, n_iters, angles, momentum, phase_init)

@@ -18,6 +18,23 @@
 // ft_gl_momentum: one thread per cell of [B][n_bins][T]: c = M (cos phi, sin phi), t = c + alpha (c - c_prev),
 // phi <- atan2(t.im, t.re), c_prev <- c; the first call of a loop stores c_prev only.  Rows of T floats need not be 16-byte
 // aligned and sincosf + atan2f dominate the 28 bytes a cell moves, so the accesses are plain coalesced 4-byte ones.
+//
+// ft_spsi_phase: the single-pass phase start (Beauregard, Harish, Wyse 2015) by the rule in include/flowtron_hip.h; a float32
+// replay on the host gives the same bits.  One workgroup of 16 waves per utterance walks the frames in tiles of FT (16; 8 at
+// n_fft 4096) frames; T is the contiguous axis, so a tile is staged in and out as runs of FT floats per bin.  In LDS a frame is
+// a row of K + 3 words (the rows of a tile then start 4 banks apart): A [FT][K + 3] fp32 holds the magnitudes, then per bin the
+// increment of its owner, then the angle; O [FT][K + 3] the owner as 16 bits; phi [2][K] the accumulator, double-buffered.
+//   * analysis, one wave per frame, a lane owns ceil(K / 64) consecutive bins (an odd count: no bank conflicts) and walks them
+//     with a, b, c in registers.  Pass 1 only reads: the lane's first bin that stops a walk to the right, its last bin that stops
+//     a walk to the left, each with "is a peak", and the neighbours' edge magnitudes; a suffix minimum / prefix maximum over the
+//     lanes (6 shuffles each) hands every lane the nearest stop outside its bins.  Behind a barrier the forward sweep writes the
+//     owners of peaks and of left walks and a peak's increment over its magnitude (nobody reads that any more), the backward
+//     sweep the owners of right walks from the owners alone.  Behind another barrier every owned bin copies its peak's increment.
+//     No walk is longer than a lane's bins, whatever the slopes.
+//   * the recurrence, one thread per bin: owner and increment from the thread's own cell, one gather phi[owner], the wraps, the
+//     new phi and the angle; one barrier per frame.
+//   * frames at or behind n_frames[b] are not staged; their cells get 0.  No atomics, no scratch, no communication between
+//     workgroups.
 #include "common.h"
 
 // the float32 replay on the host rounds every operation on its own (dtw.hip, pitch.hip)
@@ -32,6 +49,12 @@ constexpr int NNLS_LDS_BYTES = 60 * 1024;
 constexpr float NNLS_TINY = 1e-30f;
 constexpr float NNLS_FLOOR = 1e-3f;
 constexpr int GLM_THREADS = 256;
+constexpr int SPSI_THREADS = 1024;              // 16 waves: one per frame of a tile
+constexpr int SPSI_MAX_FT = SPSI_THREADS / 64;
+constexpr int SPSI_LDS_BYTES = 128 * 1024;
+constexpr int SPSI_NONE = 0xffff;               // owner codes beside a bin number (<= 2048)
+constexpr int SPSI_RIGHT = 0xfffe;              // between the two sweeps: the stop of the walk to the right
+constexpr int SPSI_NO_STOP = 0x7fffffff;
 
 struct NnlsArgs {
     const float* s;                             // [B][n_mel][T]
@@ -182,6 +205,144 @@ __global__ __launch_bounds__(GLM_THREADS) void gl_momentum_k(const float* mag, f
     prev_im[i] = im;
 }
 
+__host__ __device__ inline size_t spsi_lds_bytes(int K, int FT) {
+    return (size_t)FT * (K + 3) * (sizeof(float) + sizeof(uint16_t)) + (size_t)2 * K * sizeof(float);
+}
+
+__global__ __launch_bounds__(SPSI_THREADS) void spsi_phase_k(const float* mag, float* phase, const int32_t* n_frames, int K, int T,
+                                                             int n_fft, int hop, int shift) {
+    extern __shared__ __align__(16) float smem[];
+    const int FT = 1 << shift, fmask = FT - 1, KP = K + 3;
+    float* A = smem;                                                // [FT][KP] magnitude -> owner's increment -> angle
+    float* phi = A + FT * KP;                                       // [2][K]   the accumulator, in turns
+    uint16_t* O = reinterpret_cast<uint16_t*>(phi + 2 * K);         // [FT][KP] owner
+    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int n = n_frames ? min(max(n_frames[b], 0), T) : T;
+    const float* mi = mag + (int64_t)b * K * T;
+    float* po = phase + (int64_t)b * K * T;
+    const int C = (K + 63) >> 6;                                    // bins of a lane
+    const int j0 = min(lane * C, K), j1 = min(j0 + C, K);
+    const float step = (float)hop / (float)n_fft, size = (float)n_fft;
+    for (int j = tid; j < 2 * K; j += SPSI_THREADS) phi[j] = 0.f;
+    int cur = 0;
+
+    for (int t0 = 0; t0 < n; t0 += FT) {
+        const int live = min(n - t0, FT);                           // frames of the tile inside the utterance
+        const int wide = min(T - t0, FT);                           // frames of the tile inside the tensors
+        for (int e = tid; e < K * FT; e += SPSI_THREADS) {
+            const int k = e >> shift, f = e & fmask;
+            if (f < live) A[f * KP + k] = mi[(int64_t)k * T + t0 + f];
+        }
+        __syncthreads();
+
+        // pass 1 (reads only): the lane's own stops and what lies beside its bins
+        const bool active = wave < live;                            // (uniform over the wave)
+        float* m = A + wave * KP;
+        uint16_t* o = O + wave * KP;
+        float left = 0.f, right = 0.f;
+        int stop_r = SPSI_NO_STOP, stop_l = -1;                     // 2 q + (0 peak, 1 not) / 2 q + (1 peak, 0 not)
+        if (active) {
+            if (j0 < j1) {
+                left = j0 > 0 ? m[j0 - 1] : 0.f;
+                right = j1 < K ? m[j1] : 0.f;
+                float a = left, bb = m[j0];
+                for (int j = j0; j < j1; ++j) {
+                    const float c = j + 1 < j1 ? m[j + 1] : right;
+                    const bool asc = j < K - 1 && bb < c, desc = j > 0 && bb < a;
+                    const bool peak = j >= 1 && j <= K - 2 && bb > a && bb > c;
+                    if (!asc && stop_r == SPSI_NO_STOP) stop_r = 2 * j + (peak ? 0 : 1);
+                    if (!desc) stop_l = 2 * j + (peak ? 1 : 0);
+                    a = bb;
+                    bb = c;
+                }
+            }
+            for (int d = 1; d < 64; d <<= 1) {                      // nearest stop in this lane or beyond it
+                const int r = __shfl_down(stop_r, d), l = __shfl_up(stop_l, d);
+                if (lane + d < 64) stop_r = min(stop_r, r);
+                if (lane >= d) stop_l = max(stop_l, l);
+            }
+            const int r = __shfl_down(stop_r, 1), l = __shfl_up(stop_l, 1);
+            stop_r = lane < 63 ? r : SPSI_NO_STOP;                  // ... beyond it only
+            stop_l = lane > 0 ? l : -1;
+        }
+        __syncthreads();
+
+        if (active && j0 < j1) {
+            float a = left, bb = m[j0];
+            int carry = stop_l;
+            for (int j = j0; j < j1; ++j) {                         // forward: peaks, walks to the left
+                const float c = j + 1 < j1 ? m[j + 1] : right;
+                const bool asc = j < K - 1 && bb < c, desc = j > 0 && bb < a;
+                const bool peak = j >= 1 && j <= K - 2 && bb > a && bb > c;
+                int own = SPSI_NONE;
+                if (peak) {
+                    const float den = (a - bb) + (c - bb);
+                    float p = (0.5f * (a - c)) / den;
+                    if (!(fabsf(p) <= 0.5f)) p = 0.f;
+                    m[j] = (float)((hop * j) & (n_fft - 1)) / size + step * p;
+                    own = j;
+                } else if (asc) {
+                    own = SPSI_RIGHT;
+                } else if (desc && carry >= 0 && (carry & 1)) {
+                    own = carry >> 1;
+                }
+                o[j] = (uint16_t)own;
+                if (!desc) carry = 2 * j + (peak ? 1 : 0);
+                a = bb;
+                bb = c;
+            }
+            carry = stop_r;
+            for (int j = j1 - 1; j >= j0; --j) {                    // backward: walks to the right
+                const int own = o[j];
+                if (own == SPSI_RIGHT)
+                    o[j] = (uint16_t)((carry & 1) ? SPSI_NONE : carry >> 1);
+                else
+                    carry = 2 * j + (own == j ? 0 : 1);
+            }
+        }
+        __syncthreads();
+        if (active)
+            for (int j = lane; j < K; j += 64) {                    // every owned bin takes its peak's increment
+                const int own = o[j];
+                if (own < K && own != j) m[j] = m[own];
+            }
+        __syncthreads();
+
+        for (int f = 0; f < live; ++f) {                            // the walk over the frames
+            const float* pc = phi + cur * K;
+            float* pn = phi + (cur ^ 1) * K;
+            for (int j = tid; j < K; j += SPSI_THREADS) {
+                const int own = O[f * KP + j];
+                float v;
+                if (own >= K) {
+                    v = pc[j];
+                } else {
+                    v = pc[own] + A[f * KP + j];
+                    v = v - rintf(v);
+                    if (own != j) {
+                        const float w = v + (((j - own) & 1) ? 0.5f : 0.0f);
+                        v = w - rintf(w);
+                    }
+                }
+                pn[j] = v;
+                A[f * KP + j] = 6.2831855f * v;
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+
+        for (int e = tid; e < K * FT; e += SPSI_THREADS) {
+            const int k = e >> shift, f = e & fmask;
+            if (f < wide) po[(int64_t)k * T + t0 + f] = f < live ? A[f * KP + k] : 0.f;
+        }
+        __syncthreads();
+    }
+
+    const int t_done = min((int)(((int64_t)n + FT - 1) >> shift << shift), T);      // whole tiles behind the utterance
+    const int behind = T - t_done;
+    for (int64_t e = tid; e < (int64_t)K * behind; e += SPSI_THREADS) po[(e / behind) * T + t_done + e % behind] = 0.f;
+}
+
 }  // namespace
 
 extern "C" int ft_mel_nnls(const float* s, const float* m0, float* m, const int32_t* n_frames, const int32_t* fb_bin0,
@@ -215,6 +376,26 @@ extern "C" int ft_gl_momentum(const float* magnitude, float* phase, float* prev_
     const int cells = n_bins * T;
     hipLaunchKernelGGL(gl_momentum_k, dim3(cdiv(cells, GLM_THREADS), B), dim3(GLM_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                        magnitude, phase, prev_re, prev_im, n_frames, cells, T, alpha, first);
+    FT_CHECK_LAUNCH();
+    return FT_OK;
+}
+
+extern "C" int ft_spsi_phase(const float* magnitude, float* phase, const int32_t* n_frames, int B, int n_fft, int hop, int T,
+                             void* stream) {
+    FT_CHECK_ARG(magnitude && phase);
+    FT_CHECK_ARG(B >= 1 && T >= 1 && hop >= 1 && hop <= n_fft);
+    FT_CHECK_ARG(B <= 65535);
+    if (n_fft < 256 || n_fft > 4096 || (n_fft & (n_fft - 1)))
+        return ft_fail(FT_EUNSUPPORTED, "%s: n_fft %d: the phase start takes a power-of-two n_fft in 256 .. 4096", __func__, n_fft);
+    const int K = n_fft / 2 + 1;
+    FT_CHECK_ARG((int64_t)K * T <= 0x7fffffff - GLM_THREADS);
+    int shift = 4;                                                  // the widest tile of at most SPSI_MAX_FT frames that fits
+    while (shift > 0 && ((1 << shift) > SPSI_MAX_FT || spsi_lds_bytes(K, 1 << shift) > (size_t)SPSI_LDS_BYTES)) --shift;
+    const size_t lds = spsi_lds_bytes(K, 1 << shift);
+    FT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(spsi_phase_k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     SPSI_LDS_BYTES));
+    hipLaunchKernelGGL(spsi_phase_k, dim3(B), dim3(SPSI_THREADS), lds, reinterpret_cast<hipStream_t>(stream), magnitude, phase,
+                       n_frames, K, T, n_fft, hop, shift);
     FT_CHECK_LAUNCH();
     return FT_OK;
 }

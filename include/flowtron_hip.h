@@ -795,6 +795,38 @@ int ft_mel_nnls(const float* s, const float* m0, float* m, const int32_t* n_fram
 int ft_gl_momentum(const float* magnitude, float* phase, float* prev_re, float* prev_im, const int32_t* n_frames, int B, int n_bins,
                    int T, float alpha, int first, void* stream);
 
+/* ---- mel -> waveform: the single-pass phase start of Griffin-Lim (SPSI: Beauregard, Harish, Wyse, "Single Pass Spectrogram
+ * Inversion", DSP 2015; csrc/vocode.hip; additive, not in the reference; a function added at ABI 15, no layout changes) ----------
+ * spsi_phase: one launch for the batch, one workgroup per utterance.  magnitude, phase [B][K][T] fp32 contiguous as the STFT
+ * kernels write them, K = n_fft / 2 + 1.  n_frames [B] device int32, clamped inside the kernel to 0 ..= T, or NULL for T frames
+ * everywhere: cells at or behind n_frames[b] hold 0 and their magnitudes are never read.
+ * The phase is kept in TURNS (cycles): a wrap is a subtraction of rintf (round half to even), and hundreds of frames of hop
+ * samples do not eat the mantissa.  Per utterance the frames t = 0, 1, .. are walked in order with an accumulator acc[K], all
+ * zeros before frame 0.  Every operation an fp32 operation rounded once (nothing is contracted into a fused multiply-add, the
+ * division is correctly rounded), the comparisons plain (a NaN makes none true), so a float32 replay on the host gives the
+ * same bits.  With m[k] = magnitude[b][k][t]:
+ *     peak:   bin k is a peak when 1 <= k <= K - 2, m[k] > m[k-1] and m[k] > m[k+1]
+ *     offset: a, b, c = m[k-1], m[k], m[k+1];  den = (a - b) + (c - b);  p = (0.5f * (a - c)) / den;  p = 0 unless |p| <= 0.5f
+ *             (that covers den = 0, inf and NaN)
+ *     inc[k] = float((hop * k) mod n_fft) / float(n_fft) + (float(hop) / float(n_fft)) * p       (turns; the whole turns of
+ *             hop * k / n_fft are taken out in integer arithmetic; quotient, quotient, product, sum)
+ *     owner of bin j: a peak owns itself.  Otherwise, if j < K - 1 and m[j] < m[j+1], the bin looks to the RIGHT: q = j + 1, and
+ *             while q < K - 1 and m[q] < m[q+1], q = q + 1; the owner is q if q is a peak, else there is none.  Otherwise, if
+ *             j > 0 and m[j] < m[j-1], it looks to the LEFT the same way: q = j - 1, and while q > 0 and m[q] < m[q-1],
+ *             q = q - 1; the owner is q if q is a peak, else none.  Otherwise none.  The side is chosen by the bin's own two
+ *             comparisons alone: a trough ascends to both sides and belongs to the right; if its walk to the right ends on a
+ *             plateau it has no owner (it does not try the left).  Plateaus, the bins of a ramp that ends at 0 or K - 1,
+ *             silent frames and NaN cells have none.
+ *     a peak k:             v = acc[k] + inc[k];  new[k] = v - rintf(v)
+ *     bin j owned by k != j: w = new[k] + (((j - k) & 1) ? 0.5f : 0.0f);  new[j] = w - rintf(w)      (the bins of a main lobe
+ *             alternate by half a turn: the frame's time origin is its first sample and the window is symmetric)
+ *     a bin without owner:  new[j] = acc[j]
+ *     phase[b][k][t] = 6.2831855f * new[k];  acc = new
+ * so |phase| <= pi (1 + 2^-23).  No atomics, no scratch, no communication between workgroups.
+ * FT_EINVAL before any device call: magnitude or phase NULL, B, T or hop < 1, hop > n_fft, B > 65535, K * T beyond 2^31 - 257.
+ * FT_EUNSUPPORTED: n_fft not a power of two in 256 .. 4096. */
+int ft_spsi_phase(const float* magnitude, float* phase, const int32_t* n_frames, int B, int n_fft, int hop, int T, void* stream);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

@@ -19,9 +19,9 @@
 #include <deque>
 #include <mutex>
 #include <unordered_map>
-
 #include "common.h"
 #include <type_traits>
+#include "decode_host.h"      // ftdec::, defined below
 
 namespace {
 

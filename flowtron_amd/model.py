@@ -9,16 +9,15 @@ CPU tensors raises (the CPU oracle is oracle/flowtron_oracle.py, test infrastruc
 """
 from __future__ import annotations
 
-import ctypes as C
 import numbers
 import os
-from typing import List, Optional
 
 import numpy as np
 import torch
 from torch import nn
 
 from . import _lib as L
+from . import decode
 from . import ops
 
 # NOTE: train.py-format checkpoints pickle the whole nn.Module; torch >= 2.6 refuses them under the default
@@ -328,16 +327,12 @@ class AR_Step(nn.Module):
         if add_gate:
             self.gate_threshold = 0.5
             self.gate_layer = LinearNorm(n_hidden + n_attn_channels, 1, bias=True, w_init_gain="sigmoid")
-        self._decode_work = None
 
     def __getstate__(self):
-        """train.py pickles the whole module into its checkpoints (train.py:131-141): the decode scratch (buffers per utterance
-        shape, the 54 MB weight image, the hand-off granules) is runtime state, not model state."""
-        d = self.__dict__.copy()
-        for k in ("_decode_bufs", "_decode_wimg", "_decode_gran", "_decode_batch_bufs", "_decode_batch_gran"):
-            d.pop(k, None)
-        d["_decode_work"] = None
-        return d
+        """train.py pickles the whole module into its checkpoints (train.py:131-141): the decode scratch (flowtron_amd.decode:
+        buffers per utterance shape, the 54 MB weight image, the hand-off granules -- every `_decode_*` attribute) is runtime
+        state, not model state."""
+        return {k: v for k, v in self.__dict__.items() if not k.startswith("_decode_")}
 
     def forward(self, mel, text, in_lens32, out_lens32, attn_prior=None, rowmap=None):
         """Teacher-forced flow. mel [T,B,M], text = encoder outputs [L,B,E].
@@ -446,126 +441,7 @@ class AR_Step(nn.Module):
         any batch, flowtron.py:775-828) decodes the utterances one after the other through the same kernels -- AR decode does not
         shard, so a batch is B replicas.  With a gate layer every utterance stops at its OWN frame (the reference's
         `if sigmoid(gate) > thr` raises for B > 1); frames behind an utterance's stop are zero, N' = the longest."""
-        N, B, M = residual.shape
-        if B != 1:
-            outs = []
-            for b_ in range(B):
-                pr = None if attn_prior is None else attn_prior[b_:b_ + 1]
-                if attns is not None:
-                    raise ValueError("forced alignments (attns=) are taken one utterance at a time")
-                outs.append(self.infer(residual[:, b_:b_ + 1].contiguous(), text[:, b_:b_ + 1].contiguous(), None, pr, use_graph))
-            n = max(o[0].shape[0] for o in outs)
-            mel = residual.new_zeros(n, B, M)
-            Lk = text.shape[0]
-            att = residual.new_zeros(n, B, 1, Lk)
-            for b_, (m_, rows) in enumerate(outs):
-                mel[:m_.shape[0], b_] = m_[:, 0]
-                if rows:
-                    att[:len(rows), b_] = torch.stack([r_.reshape(1, Lk) for r_ in rows])
-            return mel, [att[t_] for t_ in range(n)]
-        L.require_cuda(residual, text)
-        Lk = text.shape[0]
-        att = self.attention_layer
-        H = self.lstm.weight_hh_l0.shape[1]
-        A = att.key.linear_layer.weight.shape[0]
-        dev = residual.device
-        # persistent per-(N, L) buffers: the decode hipGraph bakes every pointer, so stable addresses = one capture,
-        # replayed for every later utterance of this shape
-        key = (N, Lk, str(dev))
-        if not hasattr(self, "_decode_bufs"):
-            import collections
-            self._decode_bufs = collections.OrderedDict()       # LRU over (N, L, device): a server with varied lengths stays bounded
-        bufs = self._decode_bufs.get(key)
-        if bufs is not None:
-            self._decode_bufs.move_to_end(key)
-        else:
-            while len(self._decode_bufs) >= 8:
-                self._decode_bufs.popitem(last=False)
-            f32 = dict(device=dev, dtype=torch.float32)
-            bufs = self._decode_bufs[key] = dict(K=torch.empty(Lk, A, **f32), V=torch.empty(Lk, A, **f32), res=torch.empty(N, M, **f32),
-                                                 mel=torch.empty(N, M, **f32), attn=torch.empty(N, Lk, **f32),
-                                                 n_done=torch.zeros(1, device=dev, dtype=torch.int32))
-        K, V, res, mel_out, attn_out, n_done = (bufs[k] for k in ("K", "V", "res", "mel", "attn", "n_done"))
-        K.copy_(ops.linear(text, att.key.linear_layer.weight, None).reshape(Lk, A))
-        V.copy_(ops.linear(text, att.value.linear_layer.weight, None).reshape(Lk, A))
-        res.copy_(residual.reshape(N, M))
-        attn_out.zero_()
-        prior_rows = forced_rows = None
-        if attn_prior is not None:              # [1, N, L] (flowtron.py:799 takes attn_prior[:, i])
-            prior_rows = attn_prior.reshape(-1, Lk)[:N].contiguous().float()
-            assert prior_rows.shape[0] == N, "attn_prior must cover every residual frame"
-        if attns is not None:                   # N rows of [L] (flowtron.py:798 takes attns[i])
-            forced_rows = (torch.stack([a_.reshape(-1) for a_ in attns]) if isinstance(attns, (list, tuple)) else attns.reshape(-1, Lk))
-            forced_rows = forced_rows[:N].contiguous().float()
-            assert forced_rows.shape == (N, Lk), "attns must hold one attention row per residual frame"
-        L.require_cuda(prior_rows, forced_rows)
-        cumm = self.use_cumm_attention
-        E = text.shape[2]
-        enc2d = text.reshape(Lk, E).contiguous()
-        nl = self.n_lstm_layers
-        nbytes = L.lib().ft_decode_workspace_bytes(Lk, H, A, M, E if cumm else 1, nl)
-        work = bufs.get("work")
-        if work is None or work.numel() < nbytes:
-            work = bufs["work"] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        has_gate = hasattr(self, "gate_layer")
-        if use_graph is None:
-            use_graph = os.environ.get("FLOWTRON_DECODE_GRAPH", "1") != "0"
-        a, p, d = self.attention_lstm, self.lstm, self.dense_layer.layers
-        keep = [K, V, res, enc2d, prior_rows, forced_rows]   # keep temporaries alive until the launch is enqueued
-        cc = self.attn_cond_layer if cumm else None
-        args = L.DecodeArgs(
-            L.ptr(a.weight_ih_l0), L.ptr(a.weight_hh_l0), L.ptr(a.bias_ih_l0), L.ptr(a.bias_hh_l0),
-            L.ptr(att.query.linear_layer.weight), L.ptr(att.v.linear_layer.weight), L.ptr(K), L.ptr(V),
-            L.ptr(p.weight_ih_l0), L.ptr(p.weight_hh_l0), L.ptr(p.bias_ih_l0), L.ptr(p.bias_hh_l0),
-            *([L.ptr(p.weight_ih_l1), L.ptr(p.weight_hh_l1), L.ptr(p.bias_ih_l1), L.ptr(p.bias_hh_l1)] if nl >= 2 else [None] * 4),
-            L.ptr(d[0].linear_layer.weight), L.ptr(d[0].linear_layer.bias),
-            L.ptr(d[1].linear_layer.weight), L.ptr(d[1].linear_layer.bias),
-            L.ptr(self.conv.weight), L.ptr(self.conv.bias),
-            L.ptr(self.gate_layer.linear_layer.weight) if has_gate else None,
-            L.ptr(self.gate_layer.linear_layer.bias) if has_gate else None,
-            L.ptr(res), L.ptr(mel_out), L.ptr(attn_out), L.ptr(n_done), L.ptr(work),
-            work.numel(), N, Lk, H, A, M, float(att.temperature),
-            float(self.gate_threshold) if has_gate else 2.0, int(bool(use_graph)),
-            L.ptr(cc.location_conv_hidden.conv.weight) if cumm else None, L.ptr(cc.location_conv_hidden.conv.bias) if cumm else None,
-            L.ptr(cc.location_conv_out.conv.weight) if cumm else None, L.ptr(cc.location_conv_out.conv.bias) if cumm else None,
-            L.ptr(att.key.linear_layer.weight) if cumm else None, L.ptr(enc2d) if cumm else None, E,
-            L.ptr(prior_rows), L.ptr(forced_rows), None, 0, None, None, nl, None)
-        if nl > 2:
-            # decoder layers beyond the second (any n_lstm_layers, flowtron.py:654-655): a host array of their four tensors each
-            ptrs = [L.ptr(getattr(p, "%s_l%d" % (nm, k))) for k in range(2, nl) for nm in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
-            extra = (C.c_void_p * len(ptrs))(*ptrs)
-            keep.append(extra)
-            args.extra_layers = C.cast(extra, C.c_void_p)
-        persist = None
-        if L.is16(L.mfma_mode()):               # 16-bit operand modes: bf16 images of the weights (half the bytes; fp32 activations)
-            nb = L.lib().ft_decode_wimg_bytes(H, A, M)
-            wimg = getattr(self, "_decode_wimg", None)           # one image buffer per flow, whatever the utterance shape
-            if wimg is None or wimg.numel() < nb or wimg.device != dev:
-                wimg = self._decode_wimg = torch.empty(nb, device=dev, dtype=torch.uint8)
-            args.wimg, args.wimg_bytes = L.ptr(wimg), wimg.numel()
-        if nl == 2 and os.environ.get("FLOWTRON_DECODE_PERSIST", "1") != "0" and ops.persist_usable(dev):
-            # one persistent launch per flow (csrc/decode.hip dec_persist_k) where its geometry applies: 16-bit weight images fully
-            # register-resident, or (fp32 mode = the reference's inference precision, round 4) the fp32 originals with the recurrent
-            # matrices resident and the rest streamed from the L2 / Infinity Cache
-            gran = getattr(self, "_decode_gran", None)
-            if gran is None or gran.device != dev:
-                gran = self._decode_gran = torch.empty(L.lib().ft_decode_persist_gran_bytes(), device=dev, dtype=torch.uint8)
-            persist = ops.persist_status(dev)
-            args.persist_gran, args.persist_status = L.ptr(gran), L.ptr(persist)
-        L.check(L.lib().ft_decode_flow(C.byref(args), L.stream()), "ft_decode_flow")
-        n = int(n_done.item()) if has_gate else N          # single host read per flow (the reference syncs every frame)
-        if persist is not None and not ops.check_persist_status(raise_on_failure=False):
-            # the one-launch decode did not complete (grid not co-resident): logged once by ops, the device is switched to the
-            # launch-per-step / staged kernels, and THIS flow is decoded again on the staged chain -- the caller never sees it
-            args.persist_gran, args.persist_status = None, None
-            attn_out.zero_()
-            L.check(L.lib().ft_decode_flow(C.byref(args), L.stream()), "ft_decode_flow")
-            n = int(n_done.item()) if has_gate else N
-        del keep
-        mel = mel_out[:n].clone().reshape(n, 1, M)          # the persistent buffers are overwritten by the next call
-        attn_all = attn_out[:n].clone()
-        attn_rows = [attn_all[i].reshape(1, 1, Lk) for i in range(n)]
-        return mel, attn_rows
+        return decode.infer(self, residual, text, attns, attn_prior, use_graph)
 
     def infer_batch(self, x, text, lens, in_lens=None, forced=None):
         """Sequential inverse of a batch whose utterances have their own lengths: x [T,B,M] (utterance b's frames 0 .. lens[b]-1;
@@ -580,119 +456,7 @@ class AR_Step(nn.Module):
         through ft_decode_flow_batch_forced (csrc/decode_forced.hip): no query projection, scores or softmax, only V is projected,
         and the returned attention rows are the given ones.  Bit for bit independent of the grouping; NOT bit-identical to
         infer(attns=), whose staged chain sums in another order."""
-        T, B, M = x.shape
-        Lk = text.shape[0]
-        il = list(in_lens) if in_lens is not None else [Lk] * B
-        att = self.attention_layer
-        A = att.key.linear_layer.weight.shape[0]
-        H = self.lstm.weight_hh_l0.shape[1]
-        dev = x.device
-        f32 = dict(device=dev, dtype=torch.float32)
-        NB = L.lib().ft_decode_batch_max()
-        has_gate = hasattr(self, "gate_layer")
-        out = torch.zeros(T, B, M, **f32)
-        attn = torch.zeros(T, B, 1, Lk, **f32)
-        n_done_all = torch.zeros(B, device=dev, dtype=torch.int32)
-        lim_host = torch.tensor(lens, dtype=torch.int32).pin_memory()
-        lim_all = lim_host.to(dev, non_blocking=True)
-        keys_all = torch.tensor(il, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-        if not hasattr(self, "_decode_batch_bufs"):
-            import collections
-            self._decode_batch_bufs = collections.OrderedDict()   # LRU over (nb, N, L, device), as _decode_bufs
-        gran = getattr(self, "_decode_batch_gran", None)
-        if gran is None or gran.device != dev:
-            gran = self._decode_batch_gran = torch.empty(L.lib().ft_decode_batch_gran_bytes(NB), device=dev, dtype=torch.uint8)
-        wimg = None
-        if L.is16(L.mfma_mode()):                                # bf16 weight images, rounded by the flow's first batched launch
-            nbytes = L.lib().ft_decode_wimg_bytes(H, A, M)
-            wimg = getattr(self, "_decode_wimg", None)
-            if wimg is None or wimg.numel() < nbytes or wimg.device != dev:
-                wimg = self._decode_wimg = torch.empty(nbytes, device=dev, dtype=torch.uint8)
-        a, p, d = self.attention_lstm, self.lstm, self.dense_layer.layers
-        singles, batched = [], []
-        for g0 in range(0, B, NB):
-            g = list(range(g0, min(g0 + NB, B)))
-            if len(g) == 1 and forced is None:
-                singles.append(g[0])
-                continue
-            batched.append(g)
-            nb, Ng = len(g), max(lens[b] for b in g)
-            key = (nb, Ng, Lk, str(dev))
-            bufs = self._decode_batch_bufs.get(key)
-            if bufs is not None:
-                self._decode_batch_bufs.move_to_end(key)
-            else:
-                while len(self._decode_batch_bufs) >= 8:
-                    self._decode_batch_bufs.popitem(last=False)
-                bufs = self._decode_batch_bufs[key] = dict(
-                    K=torch.empty(nb, Lk, A, **f32), V=torch.empty(nb, Lk, A, **f32), res=torch.empty(nb, Ng, M, **f32),
-                    mel=torch.empty(nb, Ng, M, **f32), attn=torch.empty(nb, Ng, Lk, **f32),
-                    n_done=torch.zeros(nb, device=dev, dtype=torch.int32))
-            K, V, res, mel_out, attn_out, n_done = (bufs[k] for k in ("K", "V", "res", "mel", "attn", "n_done"))
-            for j, b in enumerate(g):
-                # the projections of infer(), one utterance at a time over its own positions (rows behind them are not read)
-                tb = text[:il[b], b:b + 1].contiguous()
-                if forced is None:
-                    K[j, :il[b]].copy_(ops.linear(tb, att.key.linear_layer.weight, None).reshape(il[b], A))
-                V[j, :il[b]].copy_(ops.linear(tb, att.value.linear_layer.weight, None).reshape(il[b], A))
-            res.copy_(x[:Ng, g0:g0 + nb].transpose(0, 1))
-            mel_out.zero_()                                      # rows past an utterance's end are not written
-            attn_out.zero_()
-            n_lim = lim_all[g0:g0 + nb]
-            rows = None
-            if forced is not None:
-                # [nb][Ng][Lk] in a buffer of the group's own: the entry wants 16-byte aligned rows, and `forced` may be a view
-                # at any offset of the caller's tensor (a flow's slice of [F,B,N,L], a sliced batch)
-                rows = bufs.get("forced")
-                if rows is None:
-                    rows = bufs["forced"] = torch.empty(nb, Ng, Lk, **f32)
-                rows.copy_(forced[g0:g0 + nb, :Ng])
-            args = L.DecodeArgs(
-                L.ptr(a.weight_ih_l0), L.ptr(a.weight_hh_l0), L.ptr(a.bias_ih_l0), L.ptr(a.bias_hh_l0),
-                L.ptr(att.query.linear_layer.weight), L.ptr(att.v.linear_layer.weight), L.ptr(K) if forced is None else None, L.ptr(V),
-                L.ptr(p.weight_ih_l0), L.ptr(p.weight_hh_l0), L.ptr(p.bias_ih_l0), L.ptr(p.bias_hh_l0),
-                L.ptr(p.weight_ih_l1), L.ptr(p.weight_hh_l1), L.ptr(p.bias_ih_l1), L.ptr(p.bias_hh_l1),
-                L.ptr(d[0].linear_layer.weight), L.ptr(d[0].linear_layer.bias),
-                L.ptr(d[1].linear_layer.weight), L.ptr(d[1].linear_layer.bias),
-                L.ptr(self.conv.weight), L.ptr(self.conv.bias),
-                L.ptr(self.gate_layer.linear_layer.weight) if has_gate else None,
-                L.ptr(self.gate_layer.linear_layer.bias) if has_gate else None,
-                L.ptr(res), L.ptr(mel_out), L.ptr(attn_out), L.ptr(n_done), None,
-                0, Ng, Lk, H, A, M, float(att.temperature),
-                float(self.gate_threshold) if has_gate else 2.0, 0,
-                None, None, None, None, None, None, 1, None, L.ptr(rows),
-                L.ptr(wimg), wimg.numel() if wimg is not None else 0, L.ptr(gran), L.ptr(ops.persist_status(dev)), 2, None)
-            bargs = L.DecodeBatchArgs(args, nb, L.ptr(n_lim), int(len(batched) > 1))
-            keys = L.ptr(keys_all[g0:g0 + nb]) if any(il[b] < Lk for b in g) else None
-            if forced is not None:
-                L.check(L.lib().ft_decode_flow_batch_forced(C.byref(bargs), keys, L.stream()), "ft_decode_flow_batch_forced")
-            elif keys is not None:                               # texts of different lengths: a key count per utterance
-                L.check(L.lib().ft_decode_flow_batch_keys(C.byref(bargs), keys, L.stream()), "ft_decode_flow_batch_keys")
-            else:
-                L.check(L.lib().ft_decode_flow_batch(C.byref(bargs), L.stream()), "ft_decode_flow_batch")
-            # copied out on the stream: the next group may reuse these buffers
-            out[:Ng, g0:g0 + nb] = mel_out.transpose(0, 1)
-            attn[:Ng, g0:g0 + nb, 0] = attn_out.transpose(0, 1)
-            n_done_all[g0:g0 + nb] = n_done
-        n = list(lens)
-        if batched:
-            ok = ops.check_persist_status(raise_on_failure=False)
-            if has_gate and ok:
-                n = n_done_all.tolist()                          # the flow's one host read
-            if not ok:
-                # a batched launch did not complete: the device now uses the staged kernels, and these groups decode again one
-                # utterance at a time (infer() keeps its own fallback; given rows: its staged forced decode)
-                singles = sorted(singles + [b for g in batched for b in g])
-        for b in singles:
-            m_, rows = self.infer(x[:lens[b], b:b + 1].contiguous(), text[:il[b], b:b + 1].contiguous(),
-                                  None if forced is None else forced[b, :lens[b], :il[b]].contiguous().float())
-            n[b] = m_.shape[0]
-            out[:, b] = 0.0
-            attn[:, b] = 0.0
-            out[:n[b], b] = m_[:, 0]
-            if rows:
-                attn[:n[b], b, :, :il[b]] = torch.cat(rows, 0)
-        return out, attn, n
+        return decode.infer_batch(self, x, text, lens, in_lens, forced)
 
 
 class AR_Back_Step(nn.Module):
@@ -975,10 +739,7 @@ class Flowtron(nn.Module):
             m, _ = self.infer(residual[b:b + 1, :, :nf[b]], sid[b:b + 1], text[b:b + 1, :il[b]], temperature=temperature,
                               gate_threshold=gate_threshold, attns=rows)
             outs.append(m)
-        n = [int(m.shape[2]) for m in outs]
-        mel = residual.new_zeros(B, outs[0].shape[1], max(n), dtype=torch.float32)
-        for b, m in enumerate(outs):
-            mel[b, :, :n[b]] = m[0]
+        mel, n = decode.pad_mels(outs)
         return mel, torch.tensor(n, dtype=torch.int64)
 
     def infer(self, residual, speaker_ids, text, temperature=1.0, gate_threshold=0.5, attns=None, attn_prior=None,
@@ -1022,15 +783,8 @@ class Flowtron(nn.Module):
             else:
                 outs = [self._infer_one(residual[b:b + 1, :, :ol[b]], sid[b], text[b:b + 1, :il[b]], temperature, gate_threshold,
                                         None, None if attn_prior is None else attn_prior[b:b + 1, :ol[b], :il[b]]) for b in range(B)]
-                n = [int(m.shape[2]) for m, _ in outs]
-                mel = residual.new_zeros(B, outs[0][0].shape[1], max(n), dtype=torch.float32)
-                atts = [residual.new_zeros(max(n), B, 1, Lt, dtype=torch.float32) for _ in self.flows]
-                for b, (m, aw) in enumerate(outs):
-                    mel[b, :, :m.shape[2]] = m[0]
-                    for f, rows in enumerate(aw):
-                        if rows:
-                            atts[f][:len(rows), b, :, :il[b]] = torch.stack([r.reshape(1, il[b]) for r in rows])
-                aws = [[a[t] for t in range(max(n))] for a in atts]
+                mel, n = decode.pad_mels([m for m, _ in outs])
+                aws = [decode.pad_attn_rows([aw[f] for _, aw in outs], max(n), Lt, mel) for f in range(len(self.flows))]
         if return_lengths:
             return mel, aws, torch.tensor(n, dtype=torch.int64)
         return mel, aws

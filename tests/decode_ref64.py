@@ -7,7 +7,7 @@ What the decode kernels round (csrc/decode.hip, decode_batch.hip, decode_persist
   * fp32 weight mode (ft_decode_args.wimg NULL): nothing.  The staged chain streams the fp32 weights (dec_lstm_k, dec_gemv_k,
     dec_conv_k: decode.hip:107-162, :210-230, :356-364), dec_persist_k<true> keeps them in registers / LDS or streams them
     (decode.hip:439-447, :514-519) -- fp32 operands and fp32 FMAs everywhere.
-  * 16-bit modes (wimg given; model.py sets it for FT_BF16 AND FT_F16, `L.is16`, model.py:432-437 / :493-497): ftdec::make_wimg
+  * 16-bit modes (wimg given; flowtron_amd.decode sets it for FT_BF16 AND FT_F16, `L.is16`, in infer and infer_batch): ftdec::make_wimg
     (decode.hip:864-881) rounds exactly TEN matrices with f32_to_bf16_k (decode.hip:775-780: pack_bf16x2 = the hardware's
     round-to-nearest-even convert, common.h:63-67), in this order:
         attention_lstm.weight_ih_l0, attention_lstm.weight_hh_l0, attention_layer.query weight,

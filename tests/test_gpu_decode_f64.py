@@ -123,7 +123,7 @@ def _failures():
 class Watch:
     """Around the infer / infer_batch call of a row: proves which kernel decoded it.
     The library hides a persistent launch that does not complete: AR_Step.infer / infer_batch read the status word themselves, clear
-    it, switch the device to the staged kernels and decode again (model.py:449-455, :555-561), so a status check afterwards sees
+    it, switch the device to the staged kernels and decode again (flowtron_amd.decode.launch_or_staged), so a status check afterwards sees
     nothing.  What cannot be hidden: ops' failure counter, persist_usable() turning False, and the stage stamps that only
     dec_persist_k / dec_persist_batch_k write into the ft_decode_debug_prof buffer (decode.hip:561-562, decode_batch.hip:233-234;
     the staged chain never touches it).  expect = the row asked for the persistent kernel and has its geometry: it must have
@@ -183,7 +183,7 @@ def flow_setup(small, over, gate):
 
 
 def project(step, enc_dev, mode):
-    """K, V as AR_Step.infer computes them in this operand mode (model.py:381-382)"""
+    """K, V as AR_Step.infer computes them in this operand mode (flowtron_amd.decode.infer: its two ops.linear calls)"""
     from flowtron_amd import ops
     att = step.attention_layer
     with env(FLOWTRON_MFMA=mode):

@@ -697,6 +697,20 @@ class Flowtron(nn.Module):
             z = unsort(out[0].permute(1, 2, 0)).masked_fill(pad_t[:, None, :], 0.0)
             return z, maps[0], maps[1]
 
+    def log_likelihood(self, mel, speaker_ids, text, in_lens, out_lens, attn_prior=None, sigma=1.0):
+        """The exact log-density of every mel frame given text and speaker (the flow's change of variables, per utterance where
+        FlowtronLoss gives the batch mean): the same no-grad batched forward as latents() and alignments(), then one reduction on
+        the device (flowtron_amd.score, csrc/score.hip).  Arguments as for latents(): any order of the utterances, results in the
+        caller's order, eval() mode only.  -> a named tuple
+          frame_ll [B, T] float64: ln p(frame t of utterance b) in nats, in natural time -- the log_s of an AR_Back_Step, which the
+              forward hands back in that flow's reversed time, is read mirrored over the utterance's own length; 0 behind out_lens[b]
+          total [B] float64: the utterance's log-likelihood, the sum of its frames
+          nll_per_dim [B] float64: (sum z^2 / (2 sigma^2) - sum log_s) / (out_lens[b] M), FlowtronLoss's NLL restricted to the
+              utterance (no Gaussian constant): the frame-weighted mean over a batch is loss_nll.
+        NotImplementedError for a model built with n_components > 1: the mixture prior has its own likelihood."""
+        from . import score
+        return score.log_likelihood(self, mel, speaker_ids, text, in_lens, out_lens, attn_prior, sigma)
+
     def infer_aligned(self, residual, speaker_ids, text, alignment, in_lens=None, n_frames=None, temperature=1.0,
                       gate_threshold=1.0, persistent=False):
         """Decodes a batch along GIVEN alignments (durations from flowtron_amd.align, or the soft maps of alignments()):

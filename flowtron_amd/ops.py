@@ -2430,6 +2430,27 @@ def durations_to_rows(dur32, in32, n_frames, reverse=False):
 
 
 # --------------------------------------------------------------------------
+# attention diagnostics (csrc/score.hip; the frame log-likelihood beside it is bound in flowtron_amd/score.py)
+# --------------------------------------------------------------------------
+def attn_diagnostics(attn, in32, out32):
+    """attn [F,B,T,L] fp32 of ANY strides (read in place, natural time), device int32 lengths -> (peaks [F,B,T] int32, -1 behind
+    out_lens; counters [F,B,6] int32: n_attended, n_backward, n_skipped, longest_run, first_peak, last_peak; focus_sum [F,B]
+    float64)."""
+    L.require_cuda(attn, in32, out32)
+    F_, B, T, Lt = attn.shape
+    dev = attn.device
+    peaks = torch.empty(F_, B, T, device=dev, dtype=torch.int32)
+    counters = torch.empty(F_, B, 6, device=dev, dtype=torch.int32)
+    focus = torch.empty(F_, B, device=dev, dtype=torch.float64)
+    nbytes = L.lib().ft_attn_diagnostics_workspace_bytes(F_, B, Lt)
+    work = torch.empty(nbytes // 4, device=dev, dtype=torch.int32)
+    sf, sb, st, sl = attn.stride()
+    L.check(L.lib().ft_attn_diagnostics(L.ptr(attn), sf, sb, st, sl, L.ptr(in32), L.ptr(out32), L.ptr(peaks), L.ptr(counters),
+                                        L.ptr(focus), L.ptr(work), nbytes, F_, B, T, Lt, L.stream()), "ft_attn_diagnostics")
+    return peaks, counters, focus
+
+
+# --------------------------------------------------------------------------
 # mel-cepstral distortion along a dynamic-time-warping path (csrc/dtw.hip)
 # --------------------------------------------------------------------------
 def mel_cepstra(mel, lens32_, dct):

@@ -827,6 +827,56 @@ int ft_gl_momentum(const float* magnitude, float* phase, float* prev_re, float* 
  * FT_EUNSUPPORTED: n_fft not a power of two in 256 .. 4096. */
 int ft_spsi_phase(const float* magnitude, float* phase, const int32_t* n_frames, int B, int n_fft, int hop, int T, void* stream);
 
+/* ---- scoring utterances: per-frame log-likelihood and attention diagnostics (csrc/score.hip; additive, not in the reference;
+ * functions added at ABI 15, no layout changes) ----------
+ * frame_loglik: the exact log-density of every mel frame under the flow, in natural time, and per-utterance totals.  z [T][B][M]
+ * fp32 contiguous as the forward leaves it; log_s = HOST array of n_ls (1 ..= 8) device pointers to [T][B][M] views with row
+ * stride ld_ls (the convention of flowtron_loss_fwd); reversed = HOST array of n_ls ints, != 0 where flow f's log_s is in that
+ * flow's reversed time (an AR_Back_Step: the utterance is flipped about its OWN length; z comes back flipped to natural time,
+ * log_s does not); out_lens [B] device int32.  With n_b = min(max(out_lens[b], 0), T), for t < n_b
+ *     ll[b][t] = -sum_m z[t][b][m]^2 / (2 sigma^2) - (M / 2) ln(2 pi sigma^2) + sum_f sum_m log_s_f[tau_f(t)][b][m]
+ *     tau_f(t) = reversed[f] ? n_b - 1 - t : t
+ * frame_ll [B][T] float64, 0 at and behind n_b; total [B] float64 = sum_t ll[b][t].  Nothing at or behind out_lens[b] is read.
+ * Arithmetic: float64 on the fp32 inputs converted exactly, every operation rounded on its own (nothing is contracted into a
+ * fused multiply-add; z^2 is exact in float64 anyway), no transcendental function on the device, in this order:
+ *     lane l = 0 .. 63 owns the channels l and l + 64:   q_l = (0 + z[l]^2) + z[l + 64]^2      (a channel >= M is left out)
+ *                                                        s_l = 0;  for f ascending: s_l = s_l + log_s_f[l]; s_l = s_l + log_s_f[l + 64]
+ *     the lanes meet in the butterfly  v_l = v_l + v_{l xor off}  for off = 32, 16, 8, 4, 2, 1:  Q from q, S from s
+ *     ll = ((-(Q * inv)) - c) + S        inv = 1.0 / (2.0 * sigma * sigma),  c = (M * 0.5) * log((6.283185307179586 * sigma) * sigma),
+ *                                        both formed on the host in double (libm's log)
+ *     total: p_i = ((0 + ll[i]) + ll[i + 256]) + ...  for i = 0 .. 255, then  p_i = p_i + p_{i + h}  for h = 128, 64, .., 1 and i < h;
+ *            total = p_0
+ * The orders depend on M and n_b alone -- not on B, T, the grid or the utterance's position -- so utterance b gives the same
+ * bits alone as inside any batch, and a float64 replay on the host gives the same bits.  Two launches; no atomics, no scratch.
+ * FT_EINVAL before any device call: a NULL pointer (an entry of log_s included), n_ls outside 1 ..= 8, M outside 1 ..= 128,
+ * ld_ls < M, T or B < 1, B > 65535, sigma not a positive finite number whose inv is finite.
+ *
+ * attn_diagnostics: the health of attention maps, one launch for all flows and utterances.  attn: fp32 with ELEMENT strides
+ * (flow, utterance, frame, token), so any [F][B][T][L] view is read in place, in NATURAL time; in_lens / out_lens [B] device int32,
+ * clamped inside the kernel to l = 1 ..= L tokens and n = 1 ..= T frames; nothing at or behind them is read.  Per (f, b):
+ *     peak[t] = the lowest index j < l whose value is largest: from value -inf and no index, j ascending, replace only where
+ *               row[j] > value -- a NaN never wins; a row with nothing above -inf (all zero rows do have: 0 > -inf picks j = 0;
+ *               all -inf or NaN rows) peaks at 0.   pmax[t] = row[peak[t]]
+ *     peaks [F][B][T] int32, -1 at and behind n
+ *     counters [F][B][6] int32:  [0] n_attended  = distinct tokens that are some frame's peak
+ *                                [1] n_backward  = #{t >= 1: peak[t] < peak[t-1]}
+ *                                [2] n_skipped   = sum_{t >= 1} max(peak[t] - peak[t-1] - 1, 0)       (held at 2^31 - 1)
+ *                                [3] longest_run = the longest stretch of consecutive frames with one peak
+ *                                [4] first_peak = peak[0]      [5] last_peak = peak[n-1]
+ *     focus_sum [F][B] float64 = sum_t pmax[t]: with 16 waves to the workgroup, wave w adds the frames w, w + 16, .. ascending
+ *                                from 0 in float64, then the 16 partial sums are added in wave order from 0
+ * The counters follow from peaks in integer arithmetic.  work: one bit per token, attn_diagnostics_workspace_bytes bytes (host
+ * arithmetic only; 0 for a size < 1), 4-byte aligned; contents need not be initialised (integer atomic-or inside a workgroup's
+ * own words; no float atomics).  Any T and L.
+ * FT_EINVAL before any device call: a NULL pointer, F, B, T or L < 1, F > 65535, a negative stride, work misaligned or
+ * work_bytes too small. */
+int ft_frame_loglik(const float* z, const float* const* log_s, const int32_t* reversed, int n_ls, int64_t ld_ls,
+                    const int32_t* out_lens, double sigma, double* frame_ll, double* total, int T, int B, int M, void* stream);
+size_t ft_attn_diagnostics_workspace_bytes(int F, int B, int L);
+int ft_attn_diagnostics(const float* attn, int64_t stride_f, int64_t stride_b, int64_t stride_t, int64_t stride_l,
+                        const int32_t* in_lens, const int32_t* out_lens, int32_t* peaks, int32_t* counters, double* focus_sum,
+                        void* work, size_t work_bytes, int F, int B, int T, int L, void* stream);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

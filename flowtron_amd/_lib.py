@@ -205,6 +205,9 @@ SIGNATURES = {
     "ft_dtw_ragged": ([_p, _l, _l, _l, _p, _l, _l, _l, _p, _p, _p, _p, _p, _p, _sz, _i, _i, _i, _i, _i, _p], _i),
     "ft_f0_yin_ragged": ([_p, _l, _l, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i, _f, _p], _i),
     "ft_f0_path_stats": ([_p, _l, _l, _p, _l, _l, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p], _i),
+    "ft_f0_candidates_ragged": ([_p, _l, _l, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _i, _i, _i, _i, _f, _p], _i),
+    "ft_f0_viterbi_workspace_bytes": ([_i, _i, _i], _sz),
+    "ft_f0_viterbi_ragged": ([_p] * 8 + [_sz, _i, _i, _i, _i, _i, _f, _p], _i),
     "ft_mel_nnls": ([_p] * 9 + [_i] * 6 + [_p], _i),
     "ft_gl_momentum": ([_p] * 5 + [_i, _i, _i, _f, _i, _p], _i),
     "ft_spsi_phase": ([_p, _p, _p, _i, _i, _i, _i, _p], _i),

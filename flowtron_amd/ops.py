@@ -2500,6 +2500,35 @@ def f0_yin_ragged(audio, n32, sampling_rate, hop, W, tau_min, tau_max, threshold
     return f0, ap
 
 
+def f0_candidates_ragged(audio, n32, cum, lag_edges, sampling_rate, hop, W, tau_min, tau_max, absolute_min_prob):
+    """audio [B,N] fp32 of ANY strides, device int32 sample counts, cum [101] and lag_edges [n_bins + 1] fp32 on the device ->
+    (prob [B,T,n_bins], freq [B,T,n_bins] Hz, voiced_prob [B,T]) fp32, zeros behind an utterance's frames.  One launch."""
+    L.require_cuda(audio, n32, cum, lag_edges)
+    B, N = audio.shape
+    T, n_bins = N // hop + 1, lag_edges.numel() - 1
+    prob = torch.empty(B, T, n_bins, device=audio.device, dtype=torch.float32)
+    freq = torch.empty(B, T, n_bins, device=audio.device, dtype=torch.float32)
+    voiced = torch.empty(B, T, device=audio.device, dtype=torch.float32)
+    L.check(L.lib().ft_f0_candidates_ragged(L.ptr(audio), *audio.stride(), L.ptr(n32), L.ptr(cum), L.ptr(lag_edges), L.ptr(prob),
+                                            L.ptr(freq), L.ptr(voiced), B, N, float(sampling_rate), hop, W, tau_min, tau_max, n_bins,
+                                            float(absolute_min_prob), L.stream()), "ft_f0_candidates_ragged")
+    return prob, freq, voiced
+
+
+def f0_viterbi_ragged(prob, freq, voiced, n32, transition, centres, N, hop, switch_prob):
+    """what f0_candidates_ragged wrote (contiguous), transition [2 band + 1] and centres [n_bins] fp32 on the device ->
+    f0 [B,T] fp32 Hz, 0 = unvoiced and behind an utterance's frames.  One launch."""
+    L.require_cuda(prob, freq, voiced, n32, transition, centres)
+    B, T, n_bins = prob.shape
+    f0 = torch.empty(B, T, device=prob.device, dtype=torch.float32)
+    nbytes = L.lib().ft_f0_viterbi_workspace_bytes(B, T, n_bins)
+    work = torch.empty(nbytes, device=prob.device, dtype=torch.uint8)
+    L.check(L.lib().ft_f0_viterbi_ragged(L.ptr(prob), L.ptr(freq), L.ptr(voiced), L.ptr(n32), L.ptr(transition), L.ptr(centres),
+                                         L.ptr(f0), L.ptr(work), nbytes, B, N, hop, n_bins, (transition.numel() - 1) // 2,
+                                         float(switch_prob), L.stream()), "ft_f0_viterbi_ragged")
+    return f0
+
+
 def f0_path_stats(f0_a, f0_b, path, path_len):
     """f0_a [B,Ta], f0_b [B,Tb] fp32 of ANY strides, path [B,P,2] int32 contiguous, path_len [B] int32 -> (n_both [B] int32,
     n_mismatch [B] int32, sum_sq [B] float64: squared cents over the cells where both frames are voiced)."""

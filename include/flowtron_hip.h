@@ -761,6 +761,61 @@ int ft_f0_path_stats(const float* f0_a, int64_t a_stride_b, int64_t a_stride_t, 
                      int64_t b_stride_t, const int32_t* path, const int32_t* path_len, int32_t* n_both, int32_t* n_mismatch,
                      double* sum_sq, int B, int Ta, int Tb, int P, void* stream);
 
+/* ---- F0 through noise: probabilistic YIN (Mauch & Dixon, "pYIN", ICASSP 2014; csrc/pitch.hip; additive, not in the
+ * reference; functions added at ABI 15, no layout changes) ----------
+ * Two launches with no host work between them: f0_candidates_ragged gives every frame a distribution over pitch bins,
+ * f0_viterbi_ragged takes one path through a voiced / unvoiced pitch HMM.  audio, strides, n_samples, frames, N, hop, W, tau_min
+ * and tau_max are f0_yin_ragged's, and d, s and d' are formed by the same code: the same bits.  Every arithmetic step below is
+ * one fp32 operation rounded once, nothing is contracted, divisions are correctly rounded, comparisons are plain (a NaN makes
+ * none true), so a float32 replay on the host gives the same bits; the tables are made on the host in float64 and rounded once.
+ * f0_candidates_ragged.  Tables: cum [101] fp32, cum[i] = the Beta(a, b) distribution function at i / 100 (cum[0] = 0,
+ * cum[100] = 1): the prior weight of the thresholds float(1) / 100 .. float(i) / 100; lag_edges [n_bins + 1] fp32, DESCENDING:
+ * bin k holds the lags L with lag_edges[k + 1] < L <= lag_edges[k] (lag_edges[i] = sampling_rate / (fmin 2^((i - 1/2) / (12
+ * bins_per_semitone))) where bin k is centred on fmin 2^(k / (12 bins_per_semitone)); the kernel takes no logarithm).
+ * With n(v) = how many i in 1 .. 100 have float(i) / 100.f <= v  (n(+inf) = 100), per frame:
+ *     trough:     a lag tau in tau_min ..= tau_max with d'(tau) <= d'(tau - 1) and d'(tau) < d'(tau + 1)
+ *     candidate:  walking the troughs upwards with rec = +inf, a trough with d'(tau) < rec; its weight is
+ *                 w = cum[n(rec)] - cum[n(d'(tau))]  (the thresholds it is the first trough below), then rec = d'(tau)
+ *     global minimum: least = +inf, lags ascending, d'(tau) < least takes over (the lowest lag of equals; none if no d' is below
+ *                 +inf); its weight is w = absolute_min_prob * cum[n(least)]
+ *     an entry's lag is L = float(tau) + shift with f0_yin_ragged's parabolic shift, its frequency sampling_rate / L, its bin
+ *                 the one that holds L; entries with w <= 0 or L outside the bins are dropped
+ *     prob[k] = the sum of w over the entries of bin k, from 0, candidates in ascending lag order, the global minimum last;
+ *     freq[k] = the frequency of its heaviest entry (the earliest of equals), 0 for a bin without entries
+ *     voiced_prob = sum of prob: p[l] = prob[l] + prob[l + 64] + .. ascending from 0 for l = 0 .. 63, then for h = 32, 16, .. 1:
+ *                 p[l] = p[l] + p[l + h] for l < h; the result is p[0]
+ * A frame whose window holds a non-finite sample, a frame with s(tau_max + 1) = 0 (digital silence: s is ascending) and the
+ * frames at t >= T_b have prob = freq = voiced_prob = 0.  prob, freq [B][T][n_bins], voiced_prob [B][T] fp32 contiguous.
+ * f0_viterbi_ragged.  States (bin k, x), x = 1 voiced, x = 0 unvoiced; state number j = 2 k + x.  Tables: transition
+ * [2 band + 1] fp32, transition[o] = (band + 1 - |o - band|) / (band + 1)^2, the weight of coming from bin k + o - band (bins
+ * outside 0 .. n_bins - 1 have score 0; rows at the edges are not renormalised); centres [n_bins] fp32 Hz.  stay = 1.f -
+ * switch_prob.  Per frame t of an utterance, with FLOOR = 2^-20 and CUT = 2^-64:
+ *     obs(k, 1) = max(prob[t][k], FLOOR);   obs(k, 0) = max(max(1.f - voiced_prob[t], 0) / float(n_bins), FLOOR)
+ *     t = 0:  r_0(k, x) = obs(k, x)                                             (the uniform start is a common factor: left out)
+ *     t > 0:  A(k, x) = max over o = 0 .. 2 band of r_{t-1}(k + o - band, x) * transition[o]; the lowest o of equals
+ *             keep = A(k, x) * stay;  change = A(k, 1 - x) * switch_prob;  the predecessor changes voicing when change > keep
+ *             r_t(k, x) = ((the larger) * scale_{t-1}) * obs(k, x), and 0 where that is below CUT
+ *     scale_t = the power of two 2^-e with 2^e <= max r_t < 2^(e + 1): exact, so no logarithm is taken anywhere
+ * FLOOR keeps a frame from killing every path; CUT and 2^-20 <= switch_prob <= 1 - 2^-20 keep every product a normal number,
+ * so the rule does not lean on how denormals are treated.  The path ends in the state with the largest r at the last frame,
+ * the lowest j of equals, and goes back along the recorded predecessors.  f0[t] = 0 for an unvoiced state, else freq[t][k] if
+ * that is > 0, else centres[k]; f0 is 0 at t >= T_b.  An utterance's result does not depend on its batch.
+ * work: one byte per (frame, state): (o << 1) | voicing of the predecessor; f0_viterbi_workspace_bytes bytes (host arithmetic
+ * only; 0 for a size < 1); contents need not be initialised.  One workgroup per utterance, one lane per state, one barrier
+ * per frame.  No atomics, no scratch, no communication between workgroups in either kernel.
+ * FT_EINVAL before any device call: a NULL pointer, B, N, hop, W or n_bins < 1, band < 0, a negative stride, B > 65535,
+ * sampling_rate <= 0, tau_min < 2, tau_max < tau_min, absolute_min_prob outside [0, 1], switch_prob outside [2^-20, 1 - 2^-20],
+ * work_bytes too small.  FT_EUNSUPPORTED: W > 2048, odd W, tau_max > 1022, n_bins > 512 (a lane per state), band > 63 (a byte
+ * per backpointer). */
+int ft_f0_candidates_ragged(const float* audio, int64_t stride_b, int64_t stride_n, const int32_t* n_samples, const float* cum,
+                            const float* lag_edges, float* prob, float* freq, float* voiced_prob, int B, int N,
+                            float sampling_rate, int hop, int W, int tau_min, int tau_max, int n_bins, float absolute_min_prob,
+                            void* stream);
+size_t ft_f0_viterbi_workspace_bytes(int B, int T, int n_bins);
+int ft_f0_viterbi_ragged(const float* prob, const float* freq, const float* voiced_prob, const int32_t* n_samples,
+                         const float* transition, const float* centres, float* f0, void* work, size_t work_bytes, int B, int N,
+                         int hop, int n_bins, int band, float switch_prob, void* stream);
+
 /* ---- mel -> waveform: NNLS mel inversion and the fast Griffin-Lim momentum step (csrc/vocode.hip; additive, not in the
  * reference; functions added at ABI 15) ----------
  * mel_nnls: one launch; per frame t of utterance b, min ||W m - s||^2 over m >= 0 by n_iters (>= 0) Lee-Seung multiplicative

@@ -86,8 +86,14 @@ __global__ __launch_bounds__(256) void img_rows_k(const float* __restrict__ src,
 
 // Split image (ft_bf16_image_split3): x = hi + lo with hi = op16(x), lo = op16(x - hi) (the pair carries ~16 significand bits).  The
 // image is three column blocks of K: an ACTIVATION as [hi | lo | hi], a WEIGHT as [hi | hi | lo], so that ONE 16-bit GEMM over
-// 3 K columns yields x_hi w_hi + x_lo w_hi + x_hi w_lo = x w up to the dropped lo . lo term (2^-18): fp32-grade products at three
-// times a 16-bit GEMM's cost instead of the fp32 MFMA's sixteen.  Rows [R, Rp) and columns [3 K, Cp) are zero.  K % 8 == 0.
+// 3 K columns yields x_hi w_hi + x_lo w_hi + x_hi w_lo at three times a 16-bit GEMM's cost instead of the fp32 MFMA's sixteen.  That
+// is x w up to x_lo w_lo and the roundings of the two lo -- three terms of order u^2 |x w| (u = 2^-8 bf16, 2^-11 fp16) -- and, in
+// fp16, up to lo's absolute floor: below 2^-14 lo is a SUBNORMAL spaced 2^-24 (every lo of a weight of size 0.03 is one), so each
+// product also carries up to 2^-25 (|x| + |w|).  Not fp32-grade, then, but 2.5 to 3 digits better than 16-bit operands; measured on
+// the MI355X (tests/test_gpu_encoder_conv_f64.py: K = 320, largest deviation from the float64 product as a share of sum |x w|, the
+// plain 16-bit forward in brackets): bf16 4.2e-6, 2.8e-6, 3.4e-6 at weight scales 1, 0.03, 1e-4 (1.3e-3 to 1.4e-3); fp16 3.3e-7 at 1
+// and 4.0e-7 at 0.03 (2.0e-4), but 1.0e-4 at 1e-4 (2.0e-4): there the floor is the whole error.  tests/conv_ref64.py derives the bound.
+// Rows [R, Rp) and columns [3 K, Cp) are zero.  K % 8 == 0.
 // (Both correction terms are needed: with either one left out the encoder's worst gradient deviation reads 0.096 instead of 0.008.)
 __device__ __forceinline__ void img_split3_body(const float* __restrict__ src, long sr, int R, int K, unsigned short* __restrict__ dst,
                                                 int Rp, int Cp, int weight, size_t first, size_t stride) {

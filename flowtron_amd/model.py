@@ -89,8 +89,10 @@ def encoder_operand_modes():
     if L.is16(m16) and enc32 in ("fwd", "dx", "dw", "fwd+dx"):      # one GEMM of the three in fp32 operands (which one makes the noise?)
         conv_mode = (L.FT_F32 if "fwd" in enc32 else m16, L.FT_F32 if "dx" in enc32 else m16, L.FT_F32 if "dw" in enc32 else m16)
     elif L.is16(m16) and enc32 in ("", "split"):
-        # DEFAULT in the 16-bit modes (round 5): the convolutions' FORWARD products at fp32 grade from split images (x = hi + lo:
-        # one 16-bit GEMM over [hi | lo | hi] x [hi | hi | lo], ops.Bf16Image.split3), backward in the step's 16-bit format.
+        # DEFAULT in the 16-bit modes (round 5): the convolutions' FORWARD products from split images (x = hi + lo: one 16-bit GEMM
+        # over [hi | lo | hi] x [hi | hi | lo], ops.Bf16Image.split3), backward in the step's 16-bit format.  The products come out
+        # 2.5 to 3 digits better than 16-bit operands give (measured at this weight scale, share of sum |x w|: bf16 3e-6 for 1.4e-3,
+        # fp16 4e-7 for 2e-4; fp16's weight lo is subnormal, which caps it there: csrc/gemm_bf16.hip) -- "fp32 grade" below means that.
         # Measured on the bench batch: the 16-bit rounding of these three forward GEMMs -- renormalised by the instance norm
         # behind each -- was what made the text-embedding / encoder gradients deviate 0.11 from the fp32 oracle (the real
         # reference under bf16 autocast: 0.17); with fp32-grade forward products the worst gradient of the model reads 0.008.

@@ -932,6 +932,67 @@ int ft_attn_diagnostics(const float* attn, int64_t stride_f, int64_t stride_b, i
                         const int32_t* in_lens, const int32_t* out_lens, int32_t* peaks, int32_t* counters, double* focus_sum,
                         void* work, size_t work_bytes, int F, int B, int T, int L, void* stream);
 
+/* ---- endpoints and loudness of a zero-padded batch (csrc/level.hip; additive, not in the reference, which only divides by the
+ * peak at the end of inference.py; functions added at ABI 15, no layout changes) ----------
+ * Common to the three entries: audio is fp32 with ELEMENT strides (utterance, sample), read in place; n_samples [B] device int32,
+ * clamped inside the kernels to n = 1 ..= N; nothing at or behind n is read; utterance b gives the same bits alone as inside any
+ * batch.  start / end [B] device int32 (either may be NULL: 0 and n) name the span s = min(max(start, 0), n - 1),
+ * e = min(max(end, s + 1), n) of len = e - s >= 1 samples.  float64 arithmetic is on the fp32 samples converted exactly, every
+ * operation rounded on its own (nothing is contracted into a fused multiply-add), no transcendental function on the device.
+ *
+ * level_bounds (two launches): T = N / hop + 1 frames, utterance b has n / hop + 1.  Frame t holds the F = frame_length samples
+ * from t hop - F / 2 on, samples outside [0, n) count as 0 (librosa.effects.trim's centred framing; unpinned against librosa):
+ *     lane l = 0 .. 63:   q_l = 0;  for j = l, l + 64, .. < F ascending:  q_l = q_l + x^2      (float64; x^2 is exact)
+ *     the lanes meet in the butterfly  q_l = q_l + q_{l xor off}  for off = 32, 16, 8, 4, 2, 1;   power[b][t] = fp32(Q / F)
+ *     frame_peak[b][t] = max |x[i]| over t hop <= i < min((t + 1) hop, n)          (both 0 for t > n / hop)
+ *     ref = ref_power where it is > 0, else max_t power[b][t];   frame t is active iff  double(power) > double(threshold) * double(ref)
+ *     (the product of two fp32 is exact in float64).  With first / last the lowest / highest active frame:
+ *     start = max(first hop - pad, 0),  end = min((last + 1) hop + pad, n);   no active frame, or start >= end (the one active
+ *     frame is centred on the utterance's end): start = 0, end = n.   peak[b] = max_t frame_peak[b][t] = max |x| over [0, n), exact.
+ * power and frame_peak are [B][T] fp32, peak [B] fp32, start / end [B] int32.
+ *
+ * level_loudness (four launches): ITU-R BS.1770-4 integrated loudness of the span, one channel.  coef (HOST, 7 doubles) = the
+ * shelf's b0 b1 b2 a1 a2 and the high pass's a1 a2 (its b is 1, -2, 1) for the sampling rate; per sample x of the span, from a
+ * zero state at the span's first sample,
+ *     v = (((b0 x + b1 x1) + b2 x2) - a1 v1) - a2 v2              x1, x2 and v1, v2: the previous two inputs and shelf outputs
+ *     y = (((v - 2 v1) + v2) - h1 y1) - h2 y2                     y1, y2: the previous two outputs
+ * run as a chunked recurrence over chunks of FT_LEVEL_CHUNK = 256 samples, the state s = (v1, v2, y1, y2):
+ *     1. every chunk c from s = 0 (x1, x2 are the true samples before the chunk) -> its end state z[c]
+ *     2. s[0] = 0;  s[c + 1][r] = z[c][r] + (((M[r][0] s[c][0] + M[r][1] s[c][1]) + M[r][2] s[c][2]) + M[r][3] s[c][3])
+ *        carry (HOST, 16 doubles, row-major) = M: column j is the state after 256 steps of the recurrence with x = 0 from the j-th
+ *        unit state
+ *     3. every chunk again from s[c]; acc = acc + y^2 ascending from 0, restarted at a step boundary: a chunk gives one partial
+ *        sum to the step of its first sample and one to the next (step >= 256, so no third)
+ *     step_sums[b][k], k < len / step = the partial sums of step k's samples added ascending from 0, in sample order
+ *     block j < max(len / step - 3, 0):  z_j = ((S_j + S_{j+1}) + (S_{j+2} + S_{j+3})) / double(4 step)
+ *     G1 = {j: z_j > abs_gate};  rel = 0.1 * (sum_{G1} z_j / |G1|);  G2 = {j in G1: z_j > rel};  power = sum_{G2} z_j / |G2|
+ *        (both sums ascending from 0);  no block: NaN;  G1 empty: 0
+ * step_sums [B][max(N / step, 1)] float64 (0 behind an utterance's steps), power [B] float64, peak [B] fp32 = max |x| over the
+ * span.  work: level_loudness_workspace_bytes bytes (host arithmetic only; 0 for a size < 1), 8-byte aligned, need not be
+ * initialised.  level_gather (one launch): out [B][N] fp32 contiguous, out[b][i] = fp32(gain[b] * x[s + i]) for i < len (the plain
+ * sample where gain is NULL), 0 behind; n_out[b] = len.
+ * FT_EINVAL before any device call: a NULL pointer (but start, end, gain), B or N < 1, B > 65535, a negative stride, frame_length
+ * odd or < 2, hop outside 1 ..= frame_length, a threshold or ref_power that is negative or not finite, pad < 0, step < 1,
+ * abs_gate negative or not finite, a coefficient that is not finite, work misaligned or work_bytes too small.
+ * FT_EUNSUPPORTED: frame_length > FT_LEVEL_MAX_FRAME; step < FT_LEVEL_CHUNK (a sampling rate below 2560 Hz) or more than
+ * FT_LEVEL_MAX_STEPS steps in N (409.6 s).
+ * Measured: the replay of the three passes against scipy.signal.lfilter in float64, 1.9e-14 .. 1.5e-11 relative rms (8, 22.05,
+ * 48 kHz; chunks of 64 and 256); a full-scale 997 Hz sine at 48 kHz -3.0103 LUFS; on one MI355X, 64 utterances of 220,672
+ * samples: level_bounds 0.08 ms, level_loudness 0.29 ms (filter passes 85 + 90 us, carry 70 us, gate 11 us), the gather 17 us
+ * (profiles/level_prof.txt).  Not compared with librosa or any loudness library: neither was available. */
+#define FT_LEVEL_CHUNK 256
+#define FT_LEVEL_MAX_STEPS 4096
+#define FT_LEVEL_MAX_FRAME 4096
+int ft_level_bounds(const float* audio, int64_t stride_b, int64_t stride_n, const int32_t* n_samples, float* power,
+                    float* frame_peak, float* peak, int32_t* start, int32_t* end, int B, int N, int frame_length, int hop,
+                    float threshold, float ref_power, int pad, void* stream);
+size_t ft_level_loudness_workspace_bytes(int B, int N);
+int ft_level_loudness(const float* audio, int64_t stride_b, int64_t stride_n, const int32_t* n_samples, const int32_t* start,
+                      const int32_t* end, const double* coef, const double* carry, double abs_gate, double* step_sums,
+                      double* power, float* peak, void* work, size_t work_bytes, int B, int N, int step, void* stream);
+int ft_level_gather(const float* audio, int64_t stride_b, int64_t stride_n, const int32_t* n_samples, const int32_t* start,
+                    const int32_t* end, const float* gain, float* out, int32_t* n_out, int B, int N, void* stream);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

@@ -358,10 +358,11 @@ class AR_Step(nn.Module):
         # the gate layer reads [h_att ; ctx] like the decoder LSTM's input projection: where that projection runs over a
         # concatenated operand image, the N = 1 gate projection is taken from the same image (ops.LinearGateFn)
         g = self.gate_layer.linear_layer if hasattr(self, "gate_layer") else None
-        persist = (ops.lstm_persist_groups(B, p.weight_hh_l0.shape[1], False, mode, mel.device)
-                   or bool(ops.lstm_persist_slices(B, p.weight_hh_l0.shape[1], False, mode, mel.device))     # (B > 32: sliced launches)
-                   or ops.lstm_pad_width(B, p.weight_hh_l0.shape[1], False, mode, mel.device, T))             # (H < 1024: zero-padded twin)
-        fuse_gate = g is not None and (self.n_lstm_layers != 2 or persist or not ops.lstm2_supported(B, p.weight_hh_l0.shape[1], mode))
+        H, two = p.weight_hh_l0.shape[1], self.n_lstm_layers == 2
+        persist = ops.lstm_persistent(B, H, False, mode, mel.device) or ops.lstm_pad_width(B, H, False, mode, mel.device, T)   # (H < 1024: zero-padded twin)
+        n_pair = ops.decoder_pair_chunks(B, H, mode, mel.device, T) if (two and persist and rm is not None) else 0
+        path, fuse_gate = ops.decoder_plan(self.n_lstm_layers, g is not None, rm is not None, persist, n_pair,
+                                           two and not persist and ops.lstm2_supported(B, H, mode))
         if g is not None and not fuse_gate:
             gates = ops.linear([h_att, ctx], g.weight, g.bias, mode=mode)     # Linear over [h_att ; ctx], no concat
 
@@ -369,31 +370,27 @@ class AR_Step(nn.Module):
             r = ops.lstm_layer(h_att, out_lens32, p.weight_ih_l0, p.weight_hh_l0, p.bias_ih_l0, p.bias_hh_l0, mode=mode,
                                xs_extra=[ctx], rowmap=rm, fill="dx", gate=(g.weight, g.bias) if fuse_gate else None)
             return r if fuse_gate else (r, gates)
-        if self.n_lstm_layers != 2:
+        if path == "layers":
             # any other depth (the config schema splats n_lstm_layers into nn.LSTM, flowtron.py:655): the same per-layer pair --
             # batched input projection + one recurrence (persistent where its geometry applies) -- layer after layer
             h, gates = first_layer()
             for l in range(1, self.n_lstm_layers):
                 h = ops.lstm_layer(h, out_lens32, getattr(p, "weight_ih_l%d" % l), getattr(p, "weight_hh_l%d" % l),
                                    getattr(p, "bias_ih_l%d" % l), getattr(p, "bias_hh_l%d" % l), mode=mode, rowmap=rm)
-        elif persist and rm is not None and ops.decoder_pair_chunks(B, p.weight_hh_l0.shape[1], mode, mel.device, T):
+        elif path == "pair":
             # both layers CONCURRENTLY on four XCDs each, layer 1 one time chunk behind layer 0, the chunk's input projection between
             # the launches (ops.DecoderPairFn, csrc/lstm_roles.hip): the pair's chain of 2 T dependent steps becomes (1 + 1/n) T
-            h, gates_f = ops.decoder_pair(h_att, out_lens32, p, mode, [ctx], rm, "dx", (g.weight, g.bias) if fuse_gate else None,
-                                          ops.decoder_pair_chunks(B, p.weight_hh_l0.shape[1], mode, mel.device, T))
+            h, gates_f = ops.decoder_pair(h_att, out_lens32, p, mode, [ctx], rm, "dx", (g.weight, g.bias) if fuse_gate else None, n_pair)
             if fuse_gate:
                 gates = gates_f
-        elif persist:
-            # two persistent single-layer recurrences (csrc/lstm_persist.hip, ~2 us per step each) with layer 1's input
-            # projection as one batched GEMM between them: faster than the two-layer wavefront launch chain (~8 us per step)
-            # (the context gradient feeds the attention backward, which reduces over ALL frames: zero its padded rows)
-            h, gates = first_layer()
-            h = ops.lstm_layer(h, out_lens32, p.weight_ih_l1, p.weight_hh_l1, p.bias_ih_l1, p.bias_hh_l1, mode=mode, rowmap=rm)
-        elif ops.lstm2_supported(B, p.weight_hh_l0.shape[1], mode):
+        elif path == "lstm2":
             # both decoder layers as one software-wavefront launch chain (csrc/lstm2.hip)
             gx0 = ops.LinearFn.apply(p.weight_ih_l0, p.bias_ih_l0 + p.bias_hh_l0, L.ACT_NONE, mode, None, "", h_att, ctx)
             h = ops.LSTM2SeqFn.apply(gx0, p.weight_hh_l0, p.weight_ih_l1, p.bias_ih_l1, p.bias_hh_l1, p.weight_hh_l1, out_lens32, mode)
         else:
+            # "persistent": two persistent single-layer recurrences (csrc/lstm_persist.hip, ~2 us per step each) with layer 1's input
+            # projection as one batched GEMM between them: faster than the two-layer wavefront launch chain (~8 us per step); "step": the
+            # same on the launch-per-step kernels (the context gradient feeds the attention backward, which reduces over ALL frames: "dx")
             h, gates = first_layer()
             h = ops.lstm_layer(h, out_lens32, p.weight_ih_l1, p.weight_hh_l1, p.bias_ih_l1, p.bias_hh_l1, mode=mode, rowmap=rm)
         h = self.dense_layer(h, rowmap=rm)

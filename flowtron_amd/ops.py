@@ -299,8 +299,7 @@ def gx16_ok(mode, rowmap, T, B, H, reverse, xs, N, device):
     otherwise round to 16 bits never carries values)"""
     return (_GX16 and L.is16(mode) and rowmap is not None and not reverse and rowmap.T == T and rowmap.B == B and _PERSIST_IMG == "1"
             and linear_uses_images(mode, T * B, N, xs) and (len(xs) == 1 or _CAT_IMAGES)
-            and bool(lstm_persist_groups(B, H, reverse, mode, device) or lstm_persist_slices(B, H, reverse, mode, device))
-            and B <= 32)
+            and B <= 32 and lstm_persistent(B, H, reverse, mode, device))
 
 
 def images_apply(mode, M, N, K):
@@ -572,6 +571,17 @@ def lens_total(lens: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
 # Linear over one or two row-blocks of the weight:  y = act(sum_i x_i W[:, off_i:off_i+K_i]^T + b)
 # (nn.Linear / 1x1 Conv1d / LSTM input projection call sites, flowtron.py:568-571, :758, :767-768)
 # --------------------------------------------------------------------------
+def _dy_image(dy, w_img, rowmap, want_db):
+    """A Linear's output gradient as (image, dy): the image its producer (an LSTM backward) handed over, where it fits this node (format
+    of `w_img`, same rowmap, column sums where wanted), looked up on dy AS IT ARRIVES -- an image-only gradient is a zero-stride NaN
+    tensor (image_only_gradient) that must not be materialised.  Else (None, dy as written fp32 values).  w_img None: no image taken."""
+    img = _handoff_take(dy) if w_img is not None else None
+    if img is not None and img.fmt == w_img.fmt and img.rowmap is rowmap and not (want_db and img.colsum is None):
+        return img, dy
+    _require_written(dy)
+    return None, _c(dy.float())
+
+
 def linear_uses_images(mode, rows, N, xs):
     """whether LinearFn runs (and differentiates) this projection through shared 16-bit operand images"""
     return all(images_apply(mode, rows, N, x.shape[-1]) for x in xs) and all((x.shape[-1] % 8 == 0) for x in xs[:-1])
@@ -677,15 +687,8 @@ class LinearFn(torch.autograd.Function):
         elif ctx.imgs is None and ctx.lazy_img_mode is not None:
             lm = ctx.lazy_img_mode
             ctx.imgs = (Bf16Image(W, mode=lm), [shared_image(x, rows, x.shape[-1], lm, rowmap) for x in xs])
-        # an image handed over by the producer of dy (the LSTM backward) is looked up on dy AS IT ARRIVES: an image-only gradient is
-        # a zero-stride NaN tensor (image_only_gradient) that must not be materialised
-        d_img_in = _handoff_take(dy) if (ctx.act == L.ACT_NONE and ctx.imgs is not None) else None
-        if d_img_in is not None and (d_img_in.fmt != ctx.imgs[0].fmt or d_img_in.rowmap is not rowmap
-                                     or (ctx.has_bias and ctx.needs_input_grad[1] and d_img_in.colsum is None)):
-            d_img_in = None
-        if d_img_in is None:
-            _require_written(dy)
-            dy = _c(dy.float())
+        want_db = ctx.has_bias and ctx.needs_input_grad[1]
+        d_img_in, dy = _dy_image(dy, ctx.imgs[0] if (ctx.act == L.ACT_NONE and ctx.imgs is not None) else None, rowmap, want_db)
         # an activated layer over a row map on the image path: dpre = dy act'(pre) is formed INSIDE the conversion pass (image + bias
         # column sums, ft_bf16_image_rows_act_bwd) -- no fp32 dpre tensor
         fuse_act = ctx.act != L.ACT_NONE and ctx.imgs is not None and rowmap is not None and _FUSE_ACT_BWD
@@ -697,7 +700,6 @@ class LinearFn(torch.autograd.Function):
         dW = None
         if ctx.needs_input_grad[0]:
             dW = weight_grad_out(W) if ctx.imgs is not None else torch.empty_like(W)      # (image path: split-K with beta = 1)
-        want_db = ctx.has_bias and ctx.needs_input_grad[1]
         db = None
         dxs = []
         off = 0
@@ -817,12 +819,9 @@ class LinearGateFn(torch.autograd.Function):
             ctx.imgs = (Bf16Image.of_weight(W, ctx.mode), Bf16Image.cat_rows([x.reshape(rows, x.shape[-1]) for x in xs], ctx.mode, rowmap))
         w_img, x_cat = ctx.imgs
         want_db = ctx.has_bias and ctx.needs_input_grad[1]
-        d_img = _handoff_take(dy)                      # the LSTM backward's dgates image (possibly the ONLY form dy exists in)
-        if d_img is not None and (d_img.fmt != w_img.fmt or d_img.rowmap is not rowmap or (want_db and d_img.colsum is None)):
-            d_img = None
+        d_img, dy = _dy_image(dy, w_img, rowmap, want_db)
         if d_img is None:
-            _require_written(dy)
-            d_img = Bf16Image(_c(dy.float()).reshape(rows, N), colsum=want_db, mode=w_img.fmt, rowmap=rowmap)
+            d_img = Bf16Image(dy.reshape(rows, N), colsum=want_db, mode=w_img.fmt, rowmap=rowmap)
         db = d_img.colsum if want_db else None
         rank1 = None
         if dgate is not None:
@@ -1105,7 +1104,22 @@ def check_persist_status(raise_on_failure=True):
 PERSIST_BWD_CODE = 21        # ft_lstm_persist_bwd's one transport: the reduce-scatter kernel (csrc/lstm_persist.hip)
 
 
-def _persist_selftest(device, ng=1):
+def _persist_bwd(dy, w_hh, lens, gates, cell, dgx, d_img, mode):
+    """ONE launch of the reduce-scatter backward recurrence (csrc/lstm_persist.hip; B <= 32) over contiguous [T, B, .] tensors: dgates as
+    fp32 rows into `dgx`, as compact 16-bit image + column sums into `d_img` (over T B + B rows), or both -- one of the two may be None"""
+    T, B, H = cell.shape
+    st = _persist_watch(dy.device)
+    work = torch.empty(L.lib().ft_lstm_persist_workspace_bytes(B, H), device=dy.device, dtype=torch.uint8)
+    args = (L.ptr(dy), H, L.ptr(w_hh), L.ptr(lens), L.ptr(gates), L.ptr(cell), L.ptr(dgx), L.ptr(work), L.ptr(st.status), T, B, H, PERSIST_BWD_CODE)
+    if d_img is None:
+        L.check(L.op16("ft_lstm_persist_bwd", mode)(*args, L.stream()), "ft_lstm_persist_bwd")
+    else:
+        L.check(L.op16("ft_lstm_persist_bwd_img", mode)(*args, L.ptr(d_img.buf), d_img.ld, d_img.buf.numel() // (2 * d_img.ld), L.ptr(d_img.colsum),
+                                                        L.stream()), "ft_lstm_persist_bwd_img")
+    _persist_arm(st)
+
+
+def _persist_selftest(device):
     """tiny forward + backward through the persistent kernels the TRAINING step launches -- the roles forward at 4 and at 8 rows per
     XCD group with two roles (csrc/lstm_roles.hip: its own launch context and LDS sizes), the reduce-scatter backward once through
     ft_lstm_persist_bwd and once through the image-only entry the step itself uses (ft_lstm_persist_bwd_img) -- checked
@@ -1117,22 +1131,16 @@ def _persist_selftest(device, ng=1):
     lens = torch.full((B,), T, dtype=torch.int32, device=device)
     y, gates, cell = torch.empty(T, B, H, **f), torch.empty(T, B, 4 * H, **f), torch.empty(T, B, H, **f)
     dgx = torch.empty(T, B, 4 * H, **f)
-    work = torch.empty(L.lib().ft_lstm_persist_workspace_bytes(B, H), device=device, dtype=torch.uint8)
-    st = _persist_state(device)
-    st.usable = True                     # (roles_launch consults the state it is about to establish)
+    st = _persist_state(y.device)        # (the state the launches report to: a `device` without an index names the same card)
     try:
         wimg = roles_wimg(w, L.FT_BF16, False)
         roles_launch([fwd_role(gx, lens, y, gates, cell, wimg)], 4, L.FT_BF16, device)
         roles_launch([fwd_role(gx, lens, y, gates, cell, wimg), fwd_role(gx, lens, y, gates, cell, wimg)], 8, L.FT_BF16, device)
-        L.check(L.lib().ft_lstm_persist_bwd(L.ptr(y), H, L.ptr(w), L.ptr(lens), L.ptr(gates), L.ptr(cell), L.ptr(dgx), L.ptr(work),
-                                            L.ptr(st.status), T, B, H, PERSIST_BWD_CODE, L.stream()), "ft_lstm_persist_bwd")
+        _persist_bwd(y, w, lens, gates, cell, dgx, None, L.FT_BF16)
         if _PERSIST_IMG != "0":
-            rows, ld = T * B + B, (4 * H + 255) // 256 * 256
-            dimg = torch.empty(L.lib().ft_bf16_image_bytes(rows, 4 * H), device=device, dtype=torch.uint8)
-            dbias = torch.zeros(4 * H, **f)
-            L.check(L.lib().ft_lstm_persist_bwd_img(L.ptr(y), H, L.ptr(w), L.ptr(lens), L.ptr(gates), L.ptr(cell), None, L.ptr(work),
-                                                    L.ptr(st.status), T, B, H, PERSIST_BWD_CODE, L.ptr(dimg), ld,
-                                                    dimg.numel() // (2 * ld), L.ptr(dbias), L.stream()), "ft_lstm_persist_bwd_img")
+            dimg = Bf16Image._blank(T * B + B, 4 * H, L.FT_BF16, device)
+            dimg.colsum = torch.zeros(4 * H, **f)
+            _persist_bwd(y, w, lens, gates, cell, None, dimg, L.FT_BF16)
         ok = int(st.status.item()) == 0
     except RuntimeError:
         ok = False
@@ -1145,41 +1153,46 @@ def _persist_selftest(device, ng=1):
     return ok
 
 
-def persist_usable(device):
-    """True if the persistent kernels passed their self-test on this device (256 co-resident workgroups, XCD census)."""
-    if not L.lib().ft_lstm_persist_supported(8, 1024):
-        return False
-    st = _persist_state(torch.device(device))
+def _persist_env():
+    """FLOWTRON_LSTM_PERSIST: 1 (default), or 0 = the launch-per-step kernels (the yardstick path of the tests).  Read per call."""
+    v = int(_os.environ.get("FLOWTRON_LSTM_PERSIST", "1"))
+    if v not in (0, 1):
+        raise ValueError("FLOWTRON_LSTM_PERSIST must be 0 or 1 (the transport variants were removed in round 6)")
+    return v
+
+
+def _persist_passed(device):
+    """the self-test's verdict on this device: made at the first question, withdrawn for good by a launch that fails (_persist_failed)"""
+    st = _persist_state(device)
     if st.usable is None:
-        st.usable = _persist_selftest(torch.device(device), int(_os.environ.get("FLOWTRON_LSTM_PERSIST", "1")) or 1)
+        st.usable = _persist_selftest(device)
     return bool(st.usable)
+
+
+def persist_usable(device):
+    """True if the persistent kernels passed their self-test on this device.  FLOWTRON_LSTM_PERSIST is NOT consulted: it switches the
+    training recurrences, and the decode path, which asks here, has a switch of its own (FLOWTRON_DECODE_PERSIST)."""
+    return bool(L.lib().ft_lstm_persist_supported(8, 1024)) and _persist_passed(torch.device(device))
 
 
 def lstm_persist_groups(B, H, reverse, mode, device=None):
     """1 when the persistent recurrence kernels take this shape in one launch per sequence (H 1024, B <= 32, forward direction,
     16-bit operands, a device that passed the self-test), else 0 = the launch-per-step kernels.  FLOWTRON_LSTM_PERSIST=0 switches
-    the persistent kernels off (the yardstick path of the tests)."""
-    ng = int(_os.environ.get("FLOWTRON_LSTM_PERSIST", "1"))
-    if ng not in (0, 1):
-        raise ValueError("FLOWTRON_LSTM_PERSIST must be 0 or 1 (the transport variants were removed in round 6)")
-    if not ng or reverse or not L.is16(mode) or not L.lib().ft_lstm_persist_supported(B, H):
-        return 0
-    if device is not None:
-        st = _persist_state(device)
-        if st.usable is None:
-            st.usable = _persist_selftest(device, ng)
-        if not st.usable:
-            return 0
-    return 1
+    the persistent kernels off."""
+    return int(bool(_persist_env() and not reverse and L.is16(mode) and L.lib().ft_lstm_persist_supported(B, H)
+                    and (device is None or _persist_passed(device))))
+
+
+def lstm_persistent(B, H, reverse, mode, device):
+    """whether a persistent recurrence runs a layer of this shape: in one launch up to B 32, in slices of a wider batch (roles_plan)"""
+    return bool(lstm_persist_groups(min(B, 32), H, reverse, mode, device))
 
 
 def lstm_persist_slices(B, H, reverse, mode, device=None):
     """True for a batch wider than the 4-row kernels hold (B > 32) where the roles kernels apply: 8 rows per XCD group up to B 64, 16
     up to 128 per launch forward / slices of 64 backward (roles_plan; 1.93 us per step at B 64 against 2 x 1.76 for two sliced launches
     of the round-5 kernel, 6.8 us for the launch-per-step kernels at B 48).  False: one launch suffices, or the shape is not theirs."""
-    if B <= 32:
-        return False
-    return bool(lstm_persist_groups(32, H, reverse, mode, device))
+    return B > 32 and lstm_persistent(B, H, reverse, mode, device)
 
 
 # b_ih + b_hh of the LSTMs of a flow (and of the encoder) in ONE launch each per forward (a multi-tensor add; eight elementwise launches
@@ -1238,7 +1251,7 @@ def lstm_pad_width(B, H, reverse, mode, device, T):
     wider projection (4096 gate columns instead of 4 H)"""
     if not _PAD_H or H >= PERSIST_H or H < 256 or H % 8 or reverse or T < 64:      # (H < 256: > 4 x the gate columns and saved gates)
         return False
-    return bool(lstm_persist_groups(min(B, 32), PERSIST_H, reverse, mode, device))
+    return lstm_persistent(B, PERSIST_H, reverse, mode, device)
 
 
 def pad_gate_blocks(w, pad_cols):
@@ -1252,16 +1265,7 @@ def pad_gate_blocks(w, pad_cols):
 def bilstm_persist_ok(B, H, mode, device):
     """the encoder-shaped persistent bidirectional kernels (H 256, B <= 32, 16-bit operands) on a device whose persistent grids
     passed the self-test; FLOWTRON_LSTM_PERSIST=0 keeps the launch-per-step pair chain"""
-    # (the kernels form their groups from the XCD census like transports 1 / 9: not for the placement-independent fabric
-    # transports 8 / 4 / 2, which are what one selects on a device where the census cannot come out)
-    if int(_os.environ.get("FLOWTRON_LSTM_PERSIST", "1")) != 1:
-        return False
-    if not L.is16(mode) or not L.lib().ft_bilstm_persist_supported(B, H):
-        return False
-    st = _persist_state(device)
-    if st.usable is None:
-        st.usable = _persist_selftest(device, int(_os.environ.get("FLOWTRON_LSTM_PERSIST", "1")))
-    return bool(st.usable)
+    return bool(_persist_env() and L.is16(mode) and L.lib().ft_bilstm_persist_supported(B, H) and _persist_passed(device))
 
 
 # ---- round 6: rows per XCD group / time windows / two roles per launch (csrc/lstm_roles.hip) ------------------------------------
@@ -1362,6 +1366,20 @@ def decoder_pair_chunks(B, H, mode, device, T):
             or not images_apply(mode, 4 * H, H, (T - 1) * B)):
         return 0
     return _PAIR_CHUNKS
+
+
+def decoder_plan(n_layers, has_gate, has_rowmap, persistent, pair_chunks, lstm2_ok):
+    """(path, fuse_gate) of a flow's decoder LSTM stack (model.AR_Step.forward) from plain values: persistent = lstm_persistent or the
+    padded twin (lstm_pad_width), pair_chunks = decoder_pair_chunks.  path: "layers" = any depth but two, layer after layer; "pair" =
+    DecoderPairFn; "persistent" / "step" = two single layers; "lstm2" = LSTM2SeqFn, which alone makes layer 0's input projection
+    itself: everywhere else the gate layer rides on that projection (fuse_gate)."""
+    if n_layers != 2:
+        path = "layers"
+    elif persistent:
+        path = "pair" if has_rowmap and pair_chunks else "persistent"
+    else:
+        path = "lstm2" if lstm2_ok else "step"
+    return path, bool(has_gate and path != "lstm2")
 
 
 def _chunk_edges(T, n):
@@ -1491,20 +1509,27 @@ class DecoderPairFn(torch.autograd.Function):
         w_img = ctx.w_img if ctx.w_img is not None else Bf16Image.of_weight(saved[1], ctx.mode)     # (released by a first backward: retain_graph)
         ctx.w_img = None
         n = min(_PAIR_CHUNKS_BWD, T) if _PAIR_CHUNKS_BWD >= 0 else ctx.nchunks      # (at most T windows: none is empty, the edges rise strictly)
-        # whether dgx0 must carry real fp32 values: beside the image, which is the only form inside the node
-        keep_f32 = _PERSIST_IMG != "1" or torch.is_anomaly_enabled() or not ctx.gx_private
+        keep_f32 = _dgates_exit(ctx.gx_private)[1]      # dgx0 as real fp32 values beside the image, which is the only form inside the node
         if n == 0 or not _gather_gemm_on():
             return _pair_backward_sequential(ctx, saved, _c(dy1), w_img, keep_f32)
         return _pair_backward_pipeline(ctx, saved, _c(dy1), w_img, n, keep_f32)
 
 
-def _leave_dgates(dgx, d_img, img_only, shape, gx_dtype):
-    """What a recurrence's backward returns for its gx.  img_only: the NaN face of the dgates image `d_img` (a foreign reader sees NaN,
+def _dgates_exit(gx_private):
+    """How a persistent backward's dgates leave the node, (hand_image, keep_f32).  hand_image: the compact 16-bit image goes to the input
+    projection's backward -- FLOWTRON_LSTM_PERSIST_IMG 1: where gx is that projection's own, both: always, 0: never.  keep_f32: fp32
+    rows too -- where no image is handed, with "both", and in anomaly mode, which must find real values in every returned gradient."""
+    hand = _PERSIST_IMG != "0" and (gx_private or _PERSIST_IMG == "both")
+    return hand, not hand or _PERSIST_IMG == "both" or torch.is_anomaly_enabled()
+
+
+def _leave_dgates(dgx, d_img, shape, gx_dtype):
+    """What a recurrence's backward returns for its gx.  dgx None: the NaN face of the dgates image `d_img` (a foreign reader sees NaN,
     never unwritten memory), the image handed to the input projection's backward as the ONLY form.  Else the fp32 rows `dgx` in gx's
     dtype (16-bit gx rows, gx16_ok, in a pass that keeps fp32 dgates: autograd wants the gradient in gx's dtype, and the hand-off is
     keyed on the tensor it will carry), with `d_img` -- where there is one -- handed over beside them: the projection's backward reads
     the same dgates."""
-    if img_only:
+    if dgx is None:
         dgx = image_only_gradient(shape, d_img.buf.device, gx_dtype)
         _handoff_put_image_only(dgx, d_img)
         return dgx
@@ -1513,6 +1538,12 @@ def _leave_dgates(dgx, d_img, img_only, shape, gx_dtype):
     if d_img is not None:
         _handoff_put(dgx, d_img)
     return dgx
+
+
+def _compact_dw(d_img, y_img, dW, shift):
+    """dW += dgates^T y over the compact rows of the images' RowMap (split-K); shift 1 for a recurrent weight: dgates_t meets h_{t-1}"""
+    rm, H = d_img.rowmap, y_img.cols
+    gemm_img(d_img, 1, d_img.ptr(shift), y_img, 1, y_img.ptr(0), dW, d_img.cols, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=shift)
 
 
 def _pair_weight_grads(ctx, saved, d_img1, d_img0):
@@ -1527,18 +1558,16 @@ def _pair_weight_grads(ctx, saved, d_img1, d_img0):
     outs = [weight_grad_out(w) if on else None for on, w, _, _, _ in jobs]
     for dW, (on, _, d, y, shift) in zip(outs, jobs):
         if on:
-            gemm_img(d, 1, d.ptr(shift), y, 1, y.ptr(0), dW, 4 * H, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=shift)
+            _compact_dw(d, y, dW, shift)
     return outs
 
 
 def _pair_backward_return(ctx, saved, d_img1, d_img0, dgx0):
-    """the tail both backward forms share: the weight gradients, and dgx0 as FLOWTRON_LSTM_PERSIST_IMG says it leaves the node -- the image
-    alone (dgx0 None: "1" with a private gx outside anomaly mode), fp32 rows with the image beside them (both, anomaly mode), or fp32
-    rows alone ("0", a gx that is not the projection's own)"""
+    """the tail both backward forms share: the weight gradients, and dgx0 as _dgates_exit says it leaves the node -- the image alone
+    (dgx0 None), fp32 rows with the image beside them, or fp32 rows alone"""
     dW_hh1, dW_ih1, dW_hh0 = _pair_weight_grads(ctx, saved, d_img1, d_img0)
     T, B, H = saved[7].shape
-    hand = _PERSIST_IMG != "0" and (ctx.gx_private or _PERSIST_IMG == "both")
-    dgx0 = _leave_dgates(dgx0, d_img0 if hand else None, dgx0 is None, (T, B, 4 * H), ctx.gx_dtype)
+    dgx0 = _leave_dgates(dgx0, d_img0 if _dgates_exit(ctx.gx_private)[0] else None, (T, B, 4 * H), ctx.gx_dtype)
     db1 = d_img1.colsum
     return dgx0, dW_hh0, dW_ih1, db1, db1, dW_hh1, None, None, None, None, None
 
@@ -1552,25 +1581,14 @@ def _pair_backward_sequential(ctx, saved, dy1, w_img, keep_f32):
     gathering GEMM kernel off (_gather_gemm_on)."""
     w_hh0, w_ih1, w_hh1, lens, y0, g0, c0, y1, g1, c1 = saved
     T, B, H = y1.shape
-    H4, mode, rm = 4 * H, ctx.mode, ctx.rowmap
-    dev = dy1.device
-    st = _persist_watch(dev)
-    code = PERSIST_BWD_CODE
-    work = torch.empty(L.lib().ft_lstm_persist_workspace_bytes(B, H), device=dev, dtype=torch.uint8)
-
-    def recurrence(dy, g, c, w_hh, dgx=None):
-        img = Bf16Image.empty_rows(H4, rm, mode, dev)
-        L.check(L.op16("ft_lstm_persist_bwd_img", mode)(L.ptr(dy), H, L.ptr(w_hh), L.ptr(lens), L.ptr(g), L.ptr(c), L.ptr(dgx), L.ptr(work), L.ptr(st.status),
-                                                        T, B, H, code, L.ptr(img.buf), img.ld, img.buf.numel() // (2 * img.ld), L.ptr(img.colsum), L.stream()),
-                "ft_lstm_persist_bwd_img")
-        _persist_arm(st)
-        return img
-
-    d_img1 = recurrence(dy1, g1, c1, w_hh1)
+    H4, mode, rm, dev = 4 * H, ctx.mode, ctx.rowmap, dy1.device
+    d_img1 = Bf16Image.empty_rows(H4, rm, mode, dev)
+    _persist_bwd(dy1, w_hh1, lens, g1, c1, None, d_img1, mode)
     dy0 = torch.empty(T, B, H, device=dev, dtype=torch.float32)
     gemm_img(d_img1, 0, d_img1.ptr(), w_img, 1, w_img.ptr(), dy0, rm.cap, H, H4, H, rowmap=rm, compact=1)
     dgx0 = torch.empty(T, B, H4, device=dev, dtype=torch.float32) if keep_f32 else None
-    d_img0 = recurrence(dy0, g0, c0, w_hh0, dgx0)
+    d_img0 = Bf16Image.empty_rows(H4, rm, mode, dev)
+    _persist_bwd(dy0, w_hh0, lens, g0, c0, dgx0, d_img0, mode)
     return _pair_backward_return(ctx, saved, d_img1, d_img0, dgx0)
 
 
@@ -1617,21 +1635,29 @@ def _pair_backward_pipeline(ctx, saved, dy1, w_img, n, keep_f32):
     return _pair_backward_return(ctx, saved, d_img1, d_img0, dgx0)
 
 
+def _input_projection(xs, w_ih, bias, H, reverse, mode, rowmap, fill, gate):
+    """A recurrence's input projection gx = [xs] W_ih^T + bias (16-bit rows where gx16_ok allows) as (gx, gates, private).  gates: the
+    N = 1 projection of the SAME inputs by gate = (weight [1, K], bias | None), riding on this projection's image where that exists
+    (LinearGateFn).  private: gx differentiates through images over this rowmap, so its gradient may come back as the image alone."""
+    T, B, N = xs[0].shape[0], xs[0].shape[1], w_ih.shape[0]
+    gates = None
+    if gx16_ok(mode, rowmap, T, B, H, reverse, xs, N, xs[0].device):
+        fill = fill + "|c16"                   # half the bytes the projection writes and the recurrence reads
+    if gate is not None and linear_gate_fusable(mode, rowmap, xs, N):
+        gx, gates = LinearGateFn.apply(w_ih, bias, gate[0], gate[1], mode, rowmap, fill, *xs)
+    else:
+        gx = LinearFn.apply(w_ih, bias, L.ACT_NONE, mode, rowmap, fill, *xs)
+        if gate is not None:
+            gates = linear(xs, gate[0], gate[1], mode=mode)
+    private = rowmap is not None and rowmap.T == T and rowmap.B == B and linear_uses_images(mode, T * B, N, xs)
+    return gx, gates, private
+
+
 def decoder_pair(x, lens, p, mode, xs_extra, rowmap, fill, gate, nchunks):
     """the decoder nn.LSTM `p` (two layers) over [x ; xs_extra]: layer 0's input projection (with the gate layer riding on its image,
     lstm_layer) + DecoderPairFn; returns (h, gates)"""
-    xs = [x] + list(xs_extra)
-    T, B = x.shape[0], x.shape[1]
-    gates = None
-    if gx16_ok(mode, rowmap, T, B, p.weight_hh_l0.shape[1], False, xs, p.weight_ih_l0.shape[0], x.device):
-        fill = fill + "|c16"
-    if gate is not None and linear_gate_fusable(mode, rowmap, xs, p.weight_ih_l0.shape[0]):
-        gx, gates = LinearGateFn.apply(p.weight_ih_l0, bias_sum(p.bias_ih_l0, p.bias_hh_l0), gate[0], gate[1], mode, rowmap, fill, *xs)
-    else:
-        gx = LinearFn.apply(p.weight_ih_l0, bias_sum(p.bias_ih_l0, p.bias_hh_l0), L.ACT_NONE, mode, rowmap, fill, *xs)
-        if gate is not None:
-            gates = linear(xs, gate[0], gate[1], mode=mode)
-    private = rowmap is not None and rowmap.T == T and rowmap.B == B and linear_uses_images(mode, T * B, p.weight_ih_l0.shape[0], xs)
+    gx, gates, private = _input_projection([x] + list(xs_extra), p.weight_ih_l0, bias_sum(p.bias_ih_l0, p.bias_hh_l0), p.weight_hh_l0.shape[1],
+                                           False, mode, rowmap, fill, gate)
     h = DecoderPairFn.apply(gx, p.weight_hh_l0, p.weight_ih_l1, p.bias_ih_l1, p.bias_hh_l1, p.weight_hh_l1, lens, mode, rowmap, private, nchunks)
     return h, gates
 
@@ -1645,15 +1671,14 @@ class LSTMSeqFn(torch.autograd.Function):
         gx, w_hh = _c(gx), _c(w_hh)
         L.require_cuda(gx, w_hh, lens)
         T, B, H4 = gx.shape
+        H = H4 // 4
         ctx.gx_dtype = gx.dtype                       # fp32, or 16-bit rows (lstm_layer: gx16_ok) for the persistent forward kernel
-        if gx.dtype != torch.float32 and not (lstm_persist_groups(B, H4 // 4, reverse, mode, gx.device) or lstm_persist_slices(B, H4 // 4, reverse, mode, gx.device)):
+        persistent = lstm_persistent(B, H, reverse, mode, gx.device)
+        if gx.dtype != torch.float32 and not persistent:
             gx = gx.float()                           # (the device left the persistent kernels since the projection ran)
         ctx.rowmap = rowmap if (rowmap is not None and not reverse and rowmap.T == T and rowmap.B == B) else None
-        H = H4 // 4
-        y = torch.empty(T, B, H, device=gx.device, dtype=torch.float32)
-        gates = torch.empty(T, B, H4, device=gx.device, dtype=torch.float32)
-        cell = torch.empty(T, B, H, device=gx.device, dtype=torch.float32)
-        if lstm_persist_groups(B, H, reverse, mode, gx.device) or lstm_persist_slices(B, H, reverse, mode, gx.device):
+        y, gates, cell = (torch.empty(T, B, n, device=gx.device, dtype=torch.float32) for n in (H, H4, H))
+        if persistent:
             # persistent forward recurrence (csrc/lstm_roles.hip, round 6): rows per XCD group follow the batch -- B <= 32: 4 rows, ONE
             # launch per sequence (1.62 us per step; the round-5 kernel it replaced: 1.76), B <= 64: 8 rows in one launch (1.93 against
             # 2 x 1.76 for two slices), wider: slices of 128 rows at 16 per group (2.77 against 4 x 1.76).  Bit-identical to the
@@ -1670,75 +1695,67 @@ class LSTMSeqFn(torch.autograd.Function):
         return y
 
     @staticmethod
+    def _dgates_roles(ctx, saved, dy):
+        """B > 32: slices of 64 rows at 8 per XCD group (2.5 us per step against 2 x 1.65 for two 32-row launches; 16 rows per group lose in
+        the backward kernel: 7.2 us per step for 128 rows, profiles/r06_persist_rows_per_group.log)"""
+        w_hh, lens, y, gates, cell = saved
+        dgx = torch.empty_like(gates)
+        wimg = roles_wimg(w_hh, ctx.mode, True)
+        for b0, nb, R in roles_plan(y.shape[1], True):
+            roles_launch([bwd_role(dy, lens, gates, cell, dgx, wimg, b0=b0, nb=nb)], R, ctx.mode, dy.device, backward=True)
+        return dgx, None
+
+    @staticmethod
+    def _dgates_reduce_scatter(ctx, saved, dy):
+        """B <= 32: the REDUCE-SCATTER kernel (csrc/lstm_persist.hip, round 4: every CU multiplies its own dgates, fp32 partials cross the
+        XCD's L2; 1.62 us per step -- the roles backward kernel at 4 rows measures 1.71, so this one stays).  Where the image may leave
+        the node (_dgates_exit) and dW_hh runs from compact images, the output waves write the image and its column sums INSTEAD of the
+        fp32 rows (beside them where those are kept: 3.07 vs 2.91 us per step): no 450 MB dgx, no conversion pass over it."""
+        w_hh, lens, y, gates, cell = saved
+        T, B, H = y.shape
+        hand, keep_f32 = _dgates_exit(ctx.gx_private)
+        emit = hand and ctx.rowmap is not None and ctx.needs_input_grad[1] and T > 1 and images_apply(ctx.mode, 4 * H, H, (T - 1) * B)
+        d_img = Bf16Image.empty_rows(4 * H, ctx.rowmap, ctx.mode, dy.device) if emit else None
+        dgx = torch.empty_like(gates) if (keep_f32 or not emit) else None
+        _persist_bwd(dy, w_hh, lens, gates, cell, dgx, d_img, ctx.mode)
+        return dgx, d_img
+
+    @staticmethod
+    def _dgates_step(ctx, saved, dy):
+        """the launch-per-step kernels (csrc/lstm.hip): either direction, any operand format"""
+        w_hh, lens, y, gates, cell = saved
+        T, B, H = y.shape
+        dgx = torch.empty_like(gates)
+        work = torch.empty(L.lib().ft_lstm_workspace_bytes(B, H), device=dy.device, dtype=torch.uint8)
+        L.check(L.lib().ft_lstm_seq_bwd(L.ptr(dy), H, L.ptr(w_hh), L.ptr(lens), L.ptr(gates), L.ptr(cell), L.ptr(dgx),
+                                        L.ptr(work), T, B, H, int(ctx.reverse), ctx.mode, L.stream()), "ft_lstm_seq_bwd")
+        return dgx, None
+
+    @staticmethod
     def backward(ctx, dy):
-        w_hh, lens, y, gates, cell = ctx.saved_tensors
+        saved = w_hh, lens, y, gates, cell = ctx.saved_tensors
         dy = _c(dy)
         T, B, H = y.shape
-        dgx = None                                   # allocated below unless the gradient leaves as an image only
-        ng = lstm_persist_groups(B, H, ctx.reverse, ctx.mode, dy.device)
-        wide = (not ng) and lstm_persist_slices(B, H, ctx.reverse, ctx.mode, dy.device)
-        d_img, img_only = None, False
-        if wide:
-            # slices of 64 rows at 8 per XCD group (2.5 us per step against 2 x 1.65 for two 32-row launches; 16 rows per group lose in the
-            # backward kernel: 7.2 us per step for 128 rows, profiles/r06_persist_rows_per_group.log)
-            dgx = torch.empty(T, B, 4 * H, device=dy.device, dtype=torch.float32)
-            wimg = roles_wimg(w_hh, ctx.mode, True)
-            for b0, nb, R in roles_plan(B, True):
-                roles_launch([bwd_role(dy, lens, gates, cell, dgx, wimg, b0=b0, nb=nb)], R, ctx.mode, dy.device, backward=True)
-        elif ng:
-            # B <= 32: the REDUCE-SCATTER kernel (csrc/lstm_persist.hip, round 4: every CU multiplies its own dgates, fp32 partials cross
-            # the XCD's L2; 1.62 us per step -- the roles backward kernel at 4 rows measures 1.71, so this one stays)
-            ng = PERSIST_BWD_CODE
-            st = _persist_watch(dy.device)
-            work = torch.empty(L.lib().ft_lstm_persist_workspace_bytes(B, H), device=dy.device, dtype=torch.uint8)
-            rm = ctx.rowmap
-            if (_PERSIST_IMG != "0" and rm is not None and ctx.needs_input_grad[1] and T > 1 and images_apply(ctx.mode, 4 * H, H, (T - 1) * B)
-                    and (ctx.gx_private or _PERSIST_IMG == "both")):
-                # the output waves leave the compact 16-bit image of dgates and its column sums INSTEAD of the fp32 rows (beside
-                # them with FLOWTRON_LSTM_PERSIST_IMG=both: 3.07 vs 2.91 us per step): no 450 MB dgx, no conversion pass over it.
-                # Anomaly mode inspects every gradient a node returns: it gets real values (both), not the NaN face of an image.
-                d_img = Bf16Image.empty_rows(4 * H, rm, ctx.mode, dy.device)
-                img_only = _PERSIST_IMG != "both" and not torch.is_anomaly_enabled()
-                if not img_only:
-                    dgx = torch.empty(T, B, 4 * H, device=dy.device, dtype=torch.float32)
-                L.check(L.op16("ft_lstm_persist_bwd_img", ctx.mode)(L.ptr(dy), H, L.ptr(w_hh), L.ptr(lens), L.ptr(gates), L.ptr(cell),
-                                                    None if img_only else L.ptr(dgx),
-                                                    L.ptr(work), L.ptr(st.status), T, B, H, ng, L.ptr(d_img.buf), d_img.ld,
-                                                    d_img.buf.numel() // (2 * d_img.ld), L.ptr(d_img.colsum), L.stream()),
-                        "ft_lstm_persist_bwd_img")
-            else:
-                dgx = torch.empty(T, B, 4 * H, device=dy.device, dtype=torch.float32)
-                L.check(L.op16("ft_lstm_persist_bwd", ctx.mode)(L.ptr(dy), H, L.ptr(w_hh), L.ptr(lens), L.ptr(gates), L.ptr(cell), L.ptr(dgx),
-                                                    L.ptr(work), L.ptr(st.status), T, B, H, ng, L.stream()), "ft_lstm_persist_bwd")
-            _persist_arm(st)
-        else:
-            dgx = torch.empty(T, B, 4 * H, device=dy.device, dtype=torch.float32)
-            work = torch.empty(L.lib().ft_lstm_workspace_bytes(B, H), device=dy.device, dtype=torch.uint8)
-            L.check(L.lib().ft_lstm_seq_bwd(L.ptr(dy), H, L.ptr(w_hh), L.ptr(lens), L.ptr(gates), L.ptr(cell), L.ptr(dgx),
-                                            L.ptr(work), T, B, H, int(ctx.reverse), ctx.mode, L.stream()), "ft_lstm_seq_bwd")
-        dW = None
-        if ctx.needs_input_grad[1]:
-            # dW_hh[r,j] = sum_{t,b} da_t[b,r] * h_prev(t)[b,j];  h_prev = y[t-1] (fwd) / y[t+1] (reverse)
-            rows = (T - 1) * B
-            dW = weight_grad_out(w_hh)
-            rm = ctx.rowmap
-            if T > 1 and images_apply(ctx.mode, 4 * H, H, rows) and rm is not None:
+        persistent = lstm_persistent(B, H, ctx.reverse, ctx.mode, dy.device)
+        produce = LSTMSeqFn._dgates_step if not persistent else LSTMSeqFn._dgates_roles if B > 32 else LSTMSeqFn._dgates_reduce_scatter
+        dgx, d_img = produce(ctx, saved, dy)           # (fp32 rows | None, compact image | None): no rows = the image is the only form
+        # dW_hh[r,j] = sum_{t,b} da_t[b,r] * h_prev(t)[b,j];  h_prev = y[t-1] (fwd) / y[t+1] (reverse)
+        dW = weight_grad_out(w_hh) if ctx.needs_input_grad[1] else None
+        if dW is not None and T > 1:
+            rows, rm, fwd = (T - 1) * B, ctx.rowmap, not ctx.reverse
+            if not images_apply(ctx.mode, 4 * H, H, rows):
+                gemm_raw(dgx[1:] if fwd else dgx[:-1], y[:-1] if fwd else y[1:], dW, 4 * H, H, rows, 1, 4 * H, H, 1, H, mode=ctx.mode, splitk=True)
+            elif rm is not None:
                 # compact images (valid frames only, batch-major with one zero separator row per utterance): the one-step shift
                 # dgates_t <-> h_{t-1} is a shift by ONE compact row, and the utterance boundaries multiply with a separator
                 if d_img is None:
                     d_img = Bf16Image(dgx.reshape(T * B, 4 * H), colsum=True, mode=ctx.mode, rowmap=rm)
-                y_img = y_image(y, T * B, H, ctx.mode, rm)
-                gemm_img(d_img, 1, d_img.ptr(1), y_img, 1, y_img.ptr(0), dW, 4 * H, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=1)
-            elif T > 1 and images_apply(ctx.mode, 4 * H, H, rows):
+                _compact_dw(d_img, y_image(y, T * B, H, ctx.mode, rm), dW, 1)
+            else:
                 # images of dgates / outputs over all T*B rows; the one-step shift is a row offset into them
                 d_img, y_img = Bf16Image(dgx.reshape(T * B, 4 * H), colsum=True, mode=ctx.mode), shared_image(y, T * B, H, ctx.mode)
-                fwd = not ctx.reverse
                 gemm_img(d_img, 1, d_img.ptr(B if fwd else 0), y_img, 1, y_img.ptr(0 if fwd else B), dW, 4 * H, H, rows, H, beta=1.0, splitk=True)
-            elif T > 1:
-                da = dgx[1:] if not ctx.reverse else dgx[:-1]
-                hp = y[:-1] if not ctx.reverse else y[1:]
-                gemm_raw(da, hp, dW, 4 * H, H, rows, 1, 4 * H, H, 1, H, mode=ctx.mode, splitk=True)
-        return _leave_dgates(dgx, d_img, img_only, (T, B, 4 * H), ctx.gx_dtype), dW, None, None, None, None, None
+        return _leave_dgates(dgx, d_img, (T, B, 4 * H), ctx.gx_dtype), dW, None, None, None, None, None
 
 
 MAX_STEP_BATCH = 64          # batch rows the launch-per-step recurrences and the bidirectional pair chain take (csrc/lstm.hip)
@@ -1760,7 +1777,6 @@ def lstm_layer(x, lens, w_ih, w_hh, b_ih, b_hh, reverse=False, mode=None, xs_ext
     if reverse:
         rowmap = None
     T, B = x.shape[0], x.shape[1]
-    gates = None
     H = w_hh.shape[1]
     if lstm_pad_width(B, H, reverse, mode, x.device, T):
         # a hidden size below the persistent kernels' 1024 (the reference's nn.LSTM takes any, flowtron.py:654-655): the recurrence of a
@@ -1770,17 +1786,8 @@ def lstm_layer(x, lens, w_ih, w_hh, b_ih, b_hh, reverse=False, mode=None, xs_ext
         w_ih_p, w_hh_p, b_p = pad_gate_blocks(w_ih, 0), pad_gate_blocks(w_hh, PERSIST_H - H), pad_gate_blocks(bias_sum(b_ih, b_hh), 0)
         out = lstm_layer(x, lens, w_ih_p, w_hh_p, b_p, torch.zeros_like(b_p), reverse, mode, xs_extra, rowmap, fill, gate)
         return out[..., :H].contiguous() if gate is None else (out[0][..., :H].contiguous(), out[1])
-    if gx16_ok(mode, rowmap, T, B, H, reverse, xs, w_ih.shape[0], x.device):
-        fill = fill + "|c16"                   # gx as 16-bit rows: half the bytes the projection writes and the recurrence reads
-    if gate is not None and linear_gate_fusable(mode, rowmap, xs, w_ih.shape[0]):
-        # gate = (weight [1, K], bias): the N = 1 projection over the same inputs rides on this projection's image (LinearGateFn)
-        gx, gates = LinearGateFn.apply(w_ih, bias_sum(b_ih, b_hh), gate[0], gate[1], mode, rowmap, fill, *xs)
-    else:
-        gx = LinearFn.apply(w_ih, bias_sum(b_ih, b_hh), L.ACT_NONE, mode, rowmap, fill, *xs)
-        if gate is not None:
-            gates = linear(xs, gate[0], gate[1], mode=mode)
-    private = rowmap is not None and rowmap.T == T and rowmap.B == B and linear_uses_images(mode, T * B, w_ih.shape[0], xs)
-    if B > MAX_STEP_BATCH and not lstm_persist_slices(B, H, reverse, mode, gx.device):
+    gx, gates, private = _input_projection(xs, w_ih, bias_sum(b_ih, b_hh), H, reverse, mode, rowmap, fill, gate)
+    if B > MAX_STEP_BATCH and not lstm_persistent(B, H, reverse, mode, gx.device):
         # the launch-per-step kernels take at most 64 batch rows (the reference's nn.LSTM takes any, flowtron.py:654-655): the rows
         # are independent, so the recurrence runs per batch chunk on contiguous copies and autograd splits the gradients again
         h = torch.cat([LSTMSeqFn.apply(gx[:, b0:b0 + nb].contiguous(), w_hh, lens[b0:b0 + nb], reverse, mode, None, False)
@@ -1804,19 +1811,16 @@ class BiLSTMSeqFn(torch.autograd.Function):
         y = torch.empty(T, B, 2 * H, **f)
         gates = [torch.empty(T, B, H4, **f) for _ in range(2)]
         cell = [torch.empty(T, B, H, **f) for _ in range(2)]
+        args = (L.ptr(gx_f), L.ptr(gx_r), L.ptr(w_f), L.ptr(w_r), L.ptr(lens), L.ptr(y), 2 * H, L.ptr(gates[0]), L.ptr(gates[1]), L.ptr(cell[0]), L.ptr(cell[1]))
         if bilstm_persist_ok(B, H, mode, gx_f.device):
             st = _persist_watch(gx_f.device)
             work = torch.empty(L.lib().ft_bilstm_persist_workspace_bytes(B, H), device=gx_f.device, dtype=torch.uint8)
-            L.check(L.op16("ft_bilstm_persist_fwd", mode)(L.ptr(gx_f), L.ptr(gx_r), L.ptr(w_f), L.ptr(w_r), L.ptr(lens), L.ptr(y), 2 * H,
-                                                  L.ptr(gates[0]), L.ptr(gates[1]), L.ptr(cell[0]), L.ptr(cell[1]),
-                                                  L.ptr(work), L.ptr(st.status), T, B, H, L.stream()), "ft_bilstm_persist_fwd")
+            L.check(L.op16("ft_bilstm_persist_fwd", mode)(*args, L.ptr(work), L.ptr(st.status), T, B, H, L.stream()), "ft_bilstm_persist_fwd")
             _persist_arm(st, bilstm=True)
         else:
             nb = L.lib().ft_lstm_workspace_bytes(B, H)
             work = [torch.empty(nb, device=gx_f.device, dtype=torch.uint8) for _ in range(2)]
-            L.check(L.op16("ft_lstm_bidir_seq_fwd", mode)(L.ptr(gx_f), L.ptr(gx_r), L.ptr(w_f), L.ptr(w_r), L.ptr(lens), L.ptr(y), 2 * H,
-                                                  L.ptr(gates[0]), L.ptr(gates[1]), L.ptr(cell[0]), L.ptr(cell[1]),
-                                                  L.ptr(work[0]), L.ptr(work[1]), T, B, H, L.stream()), "ft_lstm_bidir_seq_fwd")
+            L.check(L.op16("ft_lstm_bidir_seq_fwd", mode)(*args, L.ptr(work[0]), L.ptr(work[1]), T, B, H, L.stream()), "ft_lstm_bidir_seq_fwd")
         ctx.save_for_backward(w_f, w_r, lens, y, gates[0], gates[1], cell[0], cell[1])
         return y
 
@@ -1828,19 +1832,16 @@ class BiLSTMSeqFn(torch.autograd.Function):
         H = H2 // 2
         f = dict(device=dy.device, dtype=torch.float32)
         dgx = [torch.empty(T, B, 4 * H, **f) for _ in range(2)]
+        args = (L.ptr(dy), 2 * H, L.ptr(w_f), L.ptr(w_r), L.ptr(lens), L.ptr(g0), L.ptr(g1), L.ptr(c0), L.ptr(c1), L.ptr(dgx[0]), L.ptr(dgx[1]))
         if bilstm_persist_ok(B, H, ctx.mode, dy.device):
             st = _persist_watch(dy.device)
             work = torch.empty(L.lib().ft_bilstm_persist_workspace_bytes(B, H), device=dy.device, dtype=torch.uint8)
-            L.check(L.op16("ft_bilstm_persist_bwd", ctx.mode)(L.ptr(dy), 2 * H, L.ptr(w_f), L.ptr(w_r), L.ptr(lens), L.ptr(g0), L.ptr(g1),
-                                                  L.ptr(c0), L.ptr(c1), L.ptr(dgx[0]), L.ptr(dgx[1]), L.ptr(work), L.ptr(st.status),
-                                                  T, B, H, L.stream()), "ft_bilstm_persist_bwd")
+            L.check(L.op16("ft_bilstm_persist_bwd", ctx.mode)(*args, L.ptr(work), L.ptr(st.status), T, B, H, L.stream()), "ft_bilstm_persist_bwd")
             _persist_arm(st, bilstm=True)
         else:
             nb = L.lib().ft_lstm_workspace_bytes(B, H)
             work = [torch.empty(nb, device=dy.device, dtype=torch.uint8) for _ in range(2)]
-            L.check(L.op16("ft_lstm_bidir_seq_bwd", ctx.mode)(L.ptr(dy), 2 * H, L.ptr(w_f), L.ptr(w_r), L.ptr(lens), L.ptr(g0), L.ptr(g1),
-                                                  L.ptr(c0), L.ptr(c1), L.ptr(dgx[0]), L.ptr(dgx[1]), L.ptr(work[0]), L.ptr(work[1]),
-                                                  T, B, H, L.stream()), "ft_lstm_bidir_seq_bwd")
+            L.check(L.op16("ft_lstm_bidir_seq_bwd", ctx.mode)(*args, L.ptr(work[0]), L.ptr(work[1]), T, B, H, L.stream()), "ft_lstm_bidir_seq_bwd")
         dWs = [None, None]
         rows = (T - 1) * B
         for d in range(2):
@@ -1859,13 +1860,12 @@ def bilstm_layer(x, lens, wf, wr, mode=None):
     mode = L.mfma_mode() if mode is None else mode
     T, B, _ = x.shape
     H = wf[1].shape[1]
-    import os
     if B > MAX_STEP_BATCH:
         # wider than the recurrence kernels take: batch chunks (independent rows; 32 rows each where the persistent bidirectional
         # kernels apply, else 64), concatenated again -- autograd splits the gradient
         cap = 32 if bilstm_persist_ok(32, H, mode, x.device) else MAX_STEP_BATCH
         return torch.cat([bilstm_layer(x[:, b0:b0 + nb], lens[b0:b0 + nb], wf, wr, mode) for b0, nb in batch_chunks(B, cap)], 1)
-    if L.is16(mode) and os.environ.get("FLOWTRON_BILSTM", "1") != "0" and L.lib().ft_lstm_bidir_supported(B, H):
+    if L.is16(mode) and _os.environ.get("FLOWTRON_BILSTM", "1") != "0" and L.lib().ft_lstm_bidir_supported(B, H):
         gx_f = LinearFn.apply(wf[0], bias_sum(wf[2], wf[3]), L.ACT_NONE, mode, None, "", x)
         gx_r = LinearFn.apply(wr[0], bias_sum(wr[2], wr[3]), L.ACT_NONE, mode, None, "", x)
         return BiLSTMSeqFn.apply(gx_f, gx_r, wf[1], wr[1], lens, mode)
@@ -2374,8 +2374,7 @@ class LSTM2SeqFn(torch.autograd.Function):
 
 
 def lstm2_supported(B, H, mode):
-    import os
-    return (L.is16(mode) and os.environ.get("FLOWTRON_LSTM2", "1") != "0" and bool(L.lib().ft_lstm2_supported(B, H)))
+    return L.is16(mode) and _os.environ.get("FLOWTRON_LSTM2", "1") != "0" and bool(L.lib().ft_lstm2_supported(B, H))
 
 
 # --------------------------------------------------------------------------

@@ -993,6 +993,55 @@ int ft_level_loudness(const float* audio, int64_t stride_b, int64_t stride_n, co
 int ft_level_gather(const float* audio, int64_t stride_b, int64_t stride_n, const int32_t* n_samples, const int32_t* start,
                     const int32_t* end, const float* gain, float* out, int32_t* n_out, int B, int N, void* stream);
 
+/* ---- pitch and pace of a zero-padded batch: time-domain pitch-synchronous overlap-add on the F0 track (csrc/prosody.hip;
+ * additive, the reference has no F0 input; functions added at ABI 15, no layout changes) ----------
+ * Two-period Hann grains are cut at analysis marks one period apart and laid down again at a new spacing: the fundamental
+ * changes, the spectral envelope stays.  Common to both entries: n_samples [B] device int32, clamped inside the kernels to
+ * n = 1 ..= N; nothing at or behind n is read; utterance b gives the same bits alone as inside any batch.  Positions are
+ * integers in units of 1 / Q sample, Q = FT_PSOLA_Q = 256; >> is the arithmetic shift, / on integers truncates; fp32 operations
+ * are rounded one at a time (nothing is contracted into a fused multiply-add), divisions correctly rounded, rint rounds halves
+ * to even.
+ *
+ * psola_marks (one launch, a wave per utterance).  f0 [B][T] fp32 Hz with ELEMENT strides (utterance, frame), frame t centred
+ * on sample t hop, T >= N / hop + 1 (further frames are never read, nor is a frame above n / hop); ratio likewise (a stride may
+ * be 0: one factor per utterance, or one for all); pace_q [B] device int32 = the pace in 1 / 65536, clamped to 16384 ..= 262144.
+ *   1. a frame is voiced iff 0 < f0[t] < inf (NaN is not).   voiced:   per[t] = int(min(max(rint(sr256 / f0[t]), 16 Q), 1024 Q)),
+ *      sr256 = fp32(256 sr);  r = ratio[t], 0.625 where not r >= 0.625, 2 where r > 2;  step[t] = max(8 Q, int(rint(float(per[t]) / r)))
+ *      unvoiced: per[t] = step[t] = unvoiced_period Q.        frame(p) = min(T - 1, ((p >> 8) + hop / 2) / hop)
+ *   2. analysis marks:  a_0 = 0,  a_{k+1} = a_k + per[frame(a_k)]  while (a_k >> 8) < n;  K of them.  The waveform is not searched
+ *      for glottal pulses: neighbouring marks exactly one period apart is what matters, and the sum gives that.
+ *   3. n_out = min(N_out, max(1, (n << 16) / pace_q)) in 64 bits.  synthesis marks:  s_0 = 0, k = 0;  while (s_j >> 8) < n_out:
+ *        ta = (s_j pace_q) >> 16 (64 bits);  k advances while k + 1 < K and |a_{k+1} - ta| <= |a_k - ta|;
+ *        synthesis[j] = s_j,  source[j] = k,  half[j] = (per[frame(a_k)] + 128) >> 8;   s_{j+1} = s_j + step[frame(ta)];  J of them.
+ * analysis [B][KA], KA >= ceil(N / 16); synthesis, source, half [B][KS], KS >= ceil(N_out / 8); n_analysis (K), n_synthesis (J),
+ * n_out [B]: device int32; entries behind K and J are not written.
+ *
+ * psola_synth (one launch, a workgroup per 256 output samples).  audio fp32 with ELEMENT strides (utterance, sample), read in
+ * place; hann [FT_PSOLA_HANN + 1] device fp32, H[i] = fp32(0.5 + 0.5 cos(pi i / 1024)) formed in float64 on the host.
+ *   4. c_j = (s_j + 128) >> 8,  m_j = (a_{source[j]} + 128) >> 8.  Output sample o < n_out takes the grains with |o - c_j| < half[j]
+ *      in ascending j, from y = wsum = 0:   d = o - c_j;  w = H[(|d| 1024) / half[j]];  wsum = wsum + w;  y = y + w x[m_j + d]
+ *      (x outside [0, n) counts as 0 and is not read);   out[o] = y / wsum where wsum >= 2^-10, else 0.
+ * out [B][N_out] fp32 contiguous, 0 at and behind n_out.  With ratio = 1 and pace_q = 65536 the synthesis marks are the analysis
+ * marks, source[j] = j, every grain reads the sample it writes, and |out - x| <= 1e-6 for |x| <= 1 (two or three products, their
+ * sum and one division: about three units in the last place).
+ * FT_EINVAL before any device call: a NULL pointer, B, N, N_out, T or hop < 1, B > 65535, a negative stride, T < N / hop + 1,
+ * KA or KS too small, sr256 not positive and finite.  FT_EUNSUPPORTED: N or N_out > FT_PSOLA_MAX_SAMPLES (positions stay below
+ * 2^31), unvoiced_period outside FT_PSOLA_MIN_PERIOD ..= FT_PSOLA_MAX_PERIOD.
+ * Measured: profiles/prosody_prof.txt.  Not compared with any outside PSOLA implementation: none was available.  The tests pin
+ * F0, envelope, length and bits, not how it sounds. */
+#define FT_PSOLA_Q 256
+#define FT_PSOLA_MIN_PERIOD 16
+#define FT_PSOLA_MAX_PERIOD 1024
+#define FT_PSOLA_MAX_SAMPLES (1 << 22)
+#define FT_PSOLA_HANN 1024
+int ft_psola_marks(const float* f0, int64_t f0_stride_b, int64_t f0_stride_t, const float* ratio, int64_t ratio_stride_b,
+                   int64_t ratio_stride_t, const int32_t* n_samples, const int32_t* pace_q, int32_t* analysis, int32_t* n_analysis,
+                   int32_t* synthesis, int32_t* source, int32_t* half, int32_t* n_synthesis, int32_t* n_out, int B, int N,
+                   int N_out, int T, int hop, int KA, int KS, float sr256, int unvoiced_period, void* stream);
+int ft_psola_synth(const float* audio, int64_t stride_b, int64_t stride_n, const int32_t* n_samples, const int32_t* analysis,
+                   const int32_t* synthesis, const int32_t* source, const int32_t* half, const int32_t* n_synthesis,
+                   const int32_t* n_out, const float* hann, float* out, int B, int N, int N_out, int KA, int KS, void* stream);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

@@ -16,6 +16,15 @@
 //   window table sits in LDS.  (|d| 1024) / half is not divided: q = int(float(|d| 1024) * (1.f / half)) is the quotient or one
 //   below it (|d| 1024 < 2^20 and the quotient < 1024, so the product is within 2^-12 of the true value, which is an integer or
 //   at least 2^-10 below the next one), and q += ((q + 1) half <= |d| 1024) makes it exact for every |d| < half <= 1024.
+// ft_psola_marks_warp: psola_marks_warp_k, the same wave per utterance, the synthesis marks walking a time map instead of
+//   s pace.  What the serial chain reads per step beyond per[] is staged too: the first PS_LDS_FRAMES entries of the map's row
+//   and, for a ratio on the output's axis, of the clamped ratio (64 KB of LDS in all; an entry behind them comes from global
+//   memory).  The output frame u of a mark is a counter like the input's (s only grows), the input frame of ta too, because the
+//   rule's running maximum keeps ta from descending.  Each step adds at least 8 Q to s, so the walk ends at n_out whatever the
+//   map, the ratio and F0 hold; u + 1 <= TM - 1 is held by a clamp besides the entry's refusal.
+// ft_psola_time_map: psola_time_map_k, a workgroup per utterance.  mid[] lives in LDS (FT_PSOLA_MAX_PATH entries): the first
+//   cell of a reference frame stores lo, after a barrier the last cell turns it into 128 hop (lo + hi) -- one writer per entry
+//   in either pass, no atomics -- and after another barrier every thread averages 2 w + 1 entries for the map entries it owns.
 // Every index is bounded by the clamped lengths and by the row capacities passed in; nothing at or behind n_samples[b] is read.
 // No atomics, no scratch.
 #include "common.h"
@@ -33,10 +42,14 @@ constexpr int PS_HANN = 1024;
 constexpr int PS_LDS_FRAMES = 4096;             // frames whose per / step the marks kernel keeps in LDS
 constexpr int PS_TILE = 256;                    // output samples (= threads) of a workgroup of the synthesis
 constexpr int PS_MIN_PACE_Q = 65536 / 4, PS_MAX_PACE_Q = 65536 * 4;
+constexpr int PS_MAX_PATH = 4096;               // cells of a warping path (and reference frames) the time map kernel holds
+constexpr int PS_MAX_SMOOTH = 32;
+constexpr int PS_MAP_THREADS = 256;
 
 static_assert(PS_Q == FT_PSOLA_Q && PS_MIN_PERIOD == FT_PSOLA_MIN_PERIOD && PS_MAX_PERIOD == FT_PSOLA_MAX_PERIOD,
               "the header names the units");
 static_assert(PS_MAX_SAMPLES == FT_PSOLA_MAX_SAMPLES && PS_HANN == FT_PSOLA_HANN, "the header names the limits");
+static_assert(PS_MAX_PATH == FT_PSOLA_MAX_PATH && PS_MAX_SMOOTH == FT_PSOLA_MAX_SMOOTH, "the header names the limits");
 
 struct MarksArgs {
     const float* f0;
@@ -67,6 +80,20 @@ __device__ __forceinline__ void psola_frame(const MarksArgs& p, int b, int t, in
         r = r >= 0.625f ? r : 0.625f;
         r = r <= 2.0f ? r : 2.0f;
         step = max(PS_MIN_PERIOD / 2 * PS_Q, (int)rintf((float)per / r));
+    } else {
+        per = step = p.unvoiced * PS_Q;
+    }
+}
+
+// per[t] alone, for a ratio that does not live on the input's frames: step = 0 on a voiced frame (the step is formed at the
+// mark, where its ratio is known), unvoiced_period Q otherwise
+__device__ __forceinline__ void psola_period(const MarksArgs& p, int b, int t, int& per, int& step) {
+    const float f = p.f0[b * p.f_sb + t * p.f_st];
+    if (f > 0.f && f <= 3.4028234663852886e38f) {
+        float q = rintf(p.sr256 / f);
+        q = fminf(fmaxf(q, (float)(PS_MIN_PERIOD * PS_Q)), (float)(PS_MAX_PERIOD * PS_Q));
+        per = (int)q;
+        step = 0;
     } else {
         per = step = p.unvoiced * PS_Q;
     }
@@ -135,6 +162,158 @@ __global__ __launch_bounds__(64) void psola_marks_k(MarksArgs p) {
         }
     }
     if (lane == 0) { p.n_amarks[b] = K; p.n_smarks[b] = J; p.n_out[b] = no; }
+}
+
+struct WarpArgs {
+    MarksArgs m;                                // (pace_q is not used; ratio is [B][RT])
+    const int32_t* n_out_in;                    // [B]
+    const int32_t* tmap;                        // [B][TM]
+    int RT, TM, hop_out, axis;
+};
+
+// the ratio as step 1 clamps it (NaN counts as 0.625)
+__device__ __forceinline__ float psola_clamp_ratio(float r) {
+    r = r >= 0.625f ? r : 0.625f;
+    return r <= 2.0f ? r : 2.0f;
+}
+
+// (d fr) / den toward zero, exactly, without the 64-bit division (a subroutine of some 150 instructions in every step of a
+// serial chain): |d| <= 2^32, 0 <= fr < den <= 2^30, inv = 1.0 / den.  |d fr| < 2^62 and the quotient is below 2^32, so the
+// double product is within 2^-19 of the true quotient: truncated it is the quotient or one off, and the remainder says which.
+__device__ __forceinline__ int64_t psola_muldiv(int64_t d, int64_t fr, int64_t den, double inv) {
+    const int64_t num = d * fr, mag = num < 0 ? -num : num;
+    int64_t q = (int64_t)((double)mag * inv);
+    const int64_t r = mag - q * den;
+    q += r >= den ? 1 : (r < 0 ? -1 : 0);
+    return num < 0 ? -q : q;
+}
+
+__global__ __launch_bounds__(64) void psola_marks_warp_k(WarpArgs w) {
+    // step_s[t]: ratio_axis 0 -- step[t] as in psola_marks_k (psola_frame); ratio_axis 1 -- psola_period's
+    __shared__ int per_s[PS_LDS_FRAMES], step_s[PS_LDS_FRAMES], map_s[PS_LDS_FRAMES];
+    __shared__ float rat_s[PS_LDS_FRAMES];
+    const MarksArgs& p = w.m;
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int n = min(max(p.n_samples[b], 1), p.N);
+    const int no = min(max(w.n_out_in[b], 1), p.N_out);
+    const int last = min(p.T - 1, n / p.hop);
+    const int u_last = min(w.TM - 2, (no - 1) / w.hop_out);                 // the highest u a mark below no 256 has
+    const int o_last = min(w.RT - 1, no / w.hop_out);                       // and the highest output frame
+    const int32_t* tm = w.tmap + (int64_t)b * w.TM;
+    const float* rrow = p.ratio + b * p.r_sb;
+    auto frame = [&](int t, int& per, int& step) {
+        if (w.axis == 1) psola_period(p, b, t, per, step); else psola_frame(p, b, t, per, step);
+    };
+    for (int t = lane; t <= min(last, PS_LDS_FRAMES - 1); t += 64) {
+        int per, step;
+        frame(t, per, step);
+        per_s[t] = per;
+        step_s[t] = step;
+    }
+    for (int u = lane; u <= min(u_last + 1, PS_LDS_FRAMES - 1); u += 64) map_s[u] = tm[u];
+    if (w.axis == 1)
+        for (int t = lane; t <= min(o_last, PS_LDS_FRAMES - 1); t += 64) rat_s[t] = psola_clamp_ratio(rrow[t * p.r_st]);
+    __syncthreads();
+    const int h2 = p.hop / 2;
+    auto fetch = [&](int t, int& per, int& step) {                          // t <= last
+        if (t < PS_LDS_FRAMES) { per = per_s[t]; step = step_s[t]; }
+        else frame(t, per, step);
+    };
+    auto map_at = [&](int u) { return u < PS_LDS_FRAMES ? map_s[u] : tm[u]; };                        // u <= TM - 1
+    auto ratio_at = [&](int t) { return t < PS_LDS_FRAMES ? rat_s[t] : psola_clamp_ratio(rrow[t * p.r_st]); };   // t <= RT - 1
+    int32_t* am = p.amarks + (int64_t)b * p.KA;
+    int32_t* sm = p.smarks + (int64_t)b * p.KS;
+    int32_t* so = p.src + (int64_t)b * p.KS;
+    int32_t* ha = p.half + (int64_t)b * p.KS;
+
+    // analysis marks: psola_marks_k's walk
+    int K = 0;
+    {
+        int a = 0, t = 0;
+        int64_t edge = p.hop;
+        while ((a >> 8) < n && K < p.KA) {
+            if (lane == 0) am[K] = a;
+            ++K;
+            while ((a >> 8) + h2 >= edge) { ++t; edge += p.hop; }
+            int per, step;
+            fetch(min(t, last), per, step);
+            a += per;
+        }
+    }
+    // synthesis marks along the map
+    int J = 0;
+    {
+        const int64_t den = (int64_t)w.hop_out * PS_Q;
+        const double inv_den = 1.0 / (double)den;
+        const int ho2 = w.hop_out / 2, ta_max = n * PS_Q - 1;
+        int s = 0, k = 0, a = 0, ta = 0, ta_t = 0, a_t = 0, per, step;
+        int u = 0, o_t = 0;
+        int64_t ta_edge = p.hop, a_edge = p.hop, u_edge = w.hop_out, o_edge = w.hop_out, u_base = 0;
+        fetch(0, per, step);
+        int an = per;
+        while ((s >> 8) < no && J < p.KS) {
+            while ((s >> 8) >= u_edge) { ++u; u_edge += w.hop_out; u_base += den; }         // u = (s >> 8) / hop_out
+            const int uc = min(u, u_last);
+            const int64_t m0 = map_at(uc), m1 = map_at(uc + 1);
+            const int64_t lin = m0 + psola_muldiv(m1 - m0, (int64_t)s - u_base, den, inv_den);
+            ta = (int)min(max(lin, (int64_t)ta), (int64_t)ta_max);                          // ta starts at 0: never below it
+            while (k + 1 < K && abs(an - ta) <= abs(a - ta)) {
+                a = an;
+                ++k;
+                while ((a >> 8) + h2 >= a_edge) { ++a_t; a_edge += p.hop; }
+                fetch(min(a_t, last), per, step);
+                an = a + per;
+            }
+            while ((ta >> 8) + h2 >= ta_edge) { ++ta_t; ta_edge += p.hop; }
+            int tper, tstep;
+            fetch(min(ta_t, last), tper, tstep);
+            if (w.axis == 1 && tstep == 0) {
+                while ((s >> 8) + ho2 >= o_edge) { ++o_t; o_edge += w.hop_out; }            // ((s >> 8) + hop_out / 2) / hop_out
+                tstep = max(PS_MIN_PERIOD / 2 * PS_Q, (int)rintf((float)tper / ratio_at(min(o_t, o_last))));
+            }
+            if (lane == 0) { sm[J] = s; so[J] = k; ha[J] = (an - a + 128) >> 8; }
+            ++J;
+            s += tstep;
+        }
+    }
+    if (lane == 0) { p.n_amarks[b] = K; p.n_smarks[b] = J; p.n_out[b] = no; }
+}
+
+struct MapArgs {
+    const int32_t* path;                        // [B][P][2]
+    const int32_t* path_len;                    // [B]
+    int32_t* tmap;                              // [B][TM]
+    int P, TM, hop, w;
+};
+
+__global__ __launch_bounds__(PS_MAP_THREADS) void psola_time_map_k(MapArgs p) {
+    __shared__ int mid[PS_MAX_PATH];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int Pb = min(max(p.path_len[b], 1), p.P);
+    const int32_t* cells = p.path + (int64_t)b * p.P * 2;
+    const int i_max = (PS_MAX_SAMPLES - 1) / p.hop, j_max = p.P - 1;
+    auto jc = [&](int c) { return min(max(cells[2 * c + 1], 0), j_max); };
+    auto ic = [&](int c) { return min(max(cells[2 * c], 0), i_max); };
+    const int Jb = jc(Pb - 1) + 1;
+    for (int j = tid; j < Jb; j += PS_MAP_THREADS) mid[j] = 0;
+    __syncthreads();
+    for (int c = tid; c < Pb; c += PS_MAP_THREADS) {
+        const int j = jc(c);
+        if (j < Jb && (c == 0 || jc(c - 1) != j)) mid[j] = ic(c);           // lo_j
+    }
+    __syncthreads();
+    for (int c = tid; c < Pb; c += PS_MAP_THREADS) {
+        const int j = jc(c);
+        if (j < Jb && (c == Pb - 1 || jc(c + 1) != j)) mid[j] = 128 * p.hop * (mid[j] + ic(c));   // hop i <= 2^22 - 1: below 2^30
+    }
+    __syncthreads();
+    int32_t* row = p.tmap + (int64_t)b * p.TM;
+    const int64_t taps = 2 * p.w + 1;
+    for (int u = tid; u < p.TM; u += PS_MAP_THREADS) {
+        int64_t sum = 0;
+        for (int d = -p.w; d <= p.w; ++d) sum += mid[min(max(u + d, 0), Jb - 1)];
+        row[u] = (int32_t)(sum / taps);
+    }
 }
 
 struct SynthArgs {
@@ -237,6 +416,55 @@ extern "C" int ft_psola_marks(const float* f0, int64_t f0_stride_b, int64_t f0_s
     p.n_out = n_out;
     p.N = N; p.N_out = N_out; p.T = T; p.hop = hop; p.KA = KA; p.KS = KS; p.unvoiced = unvoiced_period; p.sr256 = sr256;
     hipLaunchKernelGGL(psola_marks_k, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), p);
+    FT_CHECK_LAUNCH();
+    return FT_OK;
+}
+
+extern "C" int ft_psola_marks_warp(const float* f0, int64_t f0_stride_b, int64_t f0_stride_t, const float* ratio, int64_t ratio_stride_b,
+                                   int64_t ratio_stride_t, const int32_t* n_samples, const int32_t* n_out_in, const int32_t* tmap,
+                                   int32_t* analysis, int32_t* n_analysis, int32_t* synthesis, int32_t* source, int32_t* half,
+                                   int32_t* n_synthesis, int32_t* n_out, int B, int N, int N_out, int T, int RT, int TM, int hop,
+                                   int hop_out, int ratio_axis, int KA, int KS, float sr256, int unvoiced_period, void* stream) {
+    FT_CHECK_ARG(f0 && ratio && n_samples && n_out_in && tmap && analysis && n_analysis && synthesis && source && half && n_synthesis &&
+                 n_out);
+    FT_CHECK_ARG(B >= 1 && B <= 65535 && N >= 1 && N_out >= 1 && T >= 1 && RT >= 1 && TM >= 1 && hop >= 1);
+    FT_CHECK_ARG(hop_out >= 1 && hop_out <= PS_MAX_SAMPLES);
+    FT_CHECK_ARG(ratio_axis == 0 || ratio_axis == 1);
+    FT_CHECK_ARG(f0_stride_b >= 0 && f0_stride_t >= 0 && ratio_stride_b >= 0 && ratio_stride_t >= 0);
+    FT_CHECK_ARG(sr256 > 0.f && sr256 <= 3.4028234663852886e38f);
+    if (N > PS_MAX_SAMPLES || N_out > PS_MAX_SAMPLES)
+        return ft_fail(FT_EUNSUPPORTED, "%s: N %d, N_out %d: an utterance holds at most %d samples", __func__, N, N_out, PS_MAX_SAMPLES);
+    if (unvoiced_period < PS_MIN_PERIOD || unvoiced_period > PS_MAX_PERIOD)
+        return ft_fail(FT_EUNSUPPORTED, "%s: unvoiced_period %d: a period holds %d .. %d samples", __func__, unvoiced_period,
+                       PS_MIN_PERIOD, PS_MAX_PERIOD);
+    FT_CHECK_ARG(T >= N / hop + 1);
+    FT_CHECK_ARG(TM >= N_out / hop_out + 2);
+    FT_CHECK_ARG(RT >= (ratio_axis == 0 ? N / hop : N_out / hop_out) + 1);
+    FT_CHECK_ARG(KA >= cdiv(N, PS_MIN_PERIOD) && KS >= cdiv(N_out, PS_MIN_PERIOD / 2));
+    WarpArgs w{};
+    MarksArgs& p = w.m;
+    p.f0 = f0; p.f_sb = f0_stride_b; p.f_st = f0_stride_t;
+    p.ratio = ratio; p.r_sb = ratio_stride_b; p.r_st = ratio_stride_t;
+    p.n_samples = n_samples; p.pace_q = nullptr;
+    p.amarks = analysis; p.n_amarks = n_analysis; p.smarks = synthesis; p.src = source; p.half = half; p.n_smarks = n_synthesis;
+    p.n_out = n_out;
+    p.N = N; p.N_out = N_out; p.T = T; p.hop = hop; p.KA = KA; p.KS = KS; p.unvoiced = unvoiced_period; p.sr256 = sr256;
+    w.n_out_in = n_out_in; w.tmap = tmap; w.RT = RT; w.TM = TM; w.hop_out = hop_out; w.axis = ratio_axis;
+    hipLaunchKernelGGL(psola_marks_warp_k, dim3(B), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), w);
+    FT_CHECK_LAUNCH();
+    return FT_OK;
+}
+
+extern "C" int ft_psola_time_map(const int32_t* path, const int32_t* path_len, int32_t* tmap, int B, int P, int TM, int hop, int w,
+                                 void* stream) {
+    FT_CHECK_ARG(path && path_len && tmap);
+    FT_CHECK_ARG(B >= 1 && B <= 65535 && P >= 1 && TM >= 1 && hop >= 1 && hop <= PS_MAX_SAMPLES);
+    FT_CHECK_ARG(w >= 0 && w <= PS_MAX_SMOOTH);
+    if (P > PS_MAX_PATH)
+        return ft_fail(FT_EUNSUPPORTED, "%s: P %d: a path holds at most %d cells", __func__, P, PS_MAX_PATH);
+    MapArgs p{};
+    p.path = path; p.path_len = path_len; p.tmap = tmap; p.P = P; p.TM = TM; p.hop = hop; p.w = w;
+    hipLaunchKernelGGL(psola_time_map_k, dim3(B), dim3(PS_MAP_THREADS), 0, reinterpret_cast<hipStream_t>(stream), p);
     FT_CHECK_LAUNCH();
     return FT_OK;
 }

@@ -1042,6 +1042,50 @@ int ft_psola_synth(const float* audio, int64_t stride_b, int64_t stride_n, const
                    const int32_t* synthesis, const int32_t* source, const int32_t* half, const int32_t* n_synthesis,
                    const int32_t* n_out, const float* hann, float* out, int B, int N, int N_out, int KA, int KS, void* stream);
 
+/* ---- a pace that varies within the utterance: the synthesis marks walk a time map (csrc/prosody.hip; additive; functions
+ * added at ABI 15, no layout changes).  psola_synth lays the grains down from these marks unchanged ----------
+ * psola_marks_warp (one launch, a wave per utterance) is psola_marks with three differences; steps 1 and 2, per[], frame(p),
+ * the analysis marks, the source choice, half, the units and the fp32 discipline are word for word the block's above.
+ *   a. n_out_in [B] device int32 is given: n_out = min(max(n_out_in, 1), N_out).  There is no pace_q.
+ *   b. tmap [B][TM] device int32, contiguous, TM >= N_out / hop_out + 2: tmap[u] is the input position, in 1 / Q sample, that
+ *      output sample u hop_out plays.  For mark s_j, in 64 bits:   u = (s_j >> 8) / hop_out,  fr = s_j - u hop_out Q,
+ *        lin = tmap[u] + ((tmap[u + 1] - tmap[u]) fr) / (hop_out Q)          (/ truncates toward zero)
+ *        ta_j = min(max(lin, ta_{j-1}, 0), Q n - 1),  ta_{-1} = 0
+ *      The running maximum makes any map monotone as the walk sees it (a decreasing stretch holds the input still); the
+ *      clamp keeps every read in range whatever the map holds.  ta_j takes the place of (s_j pace_q) >> 16 in step 3.
+ *   c. ratio [B][RT] fp32 with element strides.  ratio_axis = 0: r_j = ratio[frame(ta_j)], the input's frame, RT >= N / hop + 1.
+ *      ratio_axis = 1: r_j = ratio[min(RT - 1, ((s_j >> 8) + hop_out / 2) / hop_out)], the OUTPUT's frame (a target contour lives
+ *      there), RT >= N_out / hop_out + 1.  r_j is clamped as in step 1 (0.625 where not r >= 0.625, 2 where r > 2).  As no frame
+ *      of f0 above n / hop is read, no entry of ratio above n_out / hop_out is (the index stops there), nor one of tmap above
+ *      (n_out - 1) / hop_out + 1: an utterance gives the same bits alone as in a longer batch.
+ *      frame(ta_j) voiced:  s_{j+1} = s_j + max(8 Q, int(rint(float(per[frame(ta_j)]) / r_j)));  unvoiced:  s_j + unvoiced_period Q.
+ * The walk ends for any contents of f0, ratio, tmap and n_out_in: every step adds at least 8 Q to s_j, J < KS, K < KA,
+ * u <= TM - 2, and ta_j < Q n bounds every frame index.  With tmap[u] = u hop Q pace (hop_out = hop, pace 1, 2 or 0.5),
+ * n_out_in = max(1, (n << 16) / pace_q) and ratio_axis = 0 the marks are psola_marks's at that pace, bit for bit.
+ * Outputs, KA and KS as psola_marks.  FT_EINVAL before any device call: psola_marks's, and hop_out < 1 or > FT_PSOLA_MAX_SAMPLES,
+ * TM < N_out / hop_out + 2, RT too small for the axis, ratio_axis not 0 or 1.  FT_EUNSUPPORTED: psola_marks's.
+ *
+ * psola_time_map (one launch, a workgroup per utterance): a warping path to such a map.  path [B][P][2] device int32, the cells
+ * (i_c, j_c) = (source frame, reference frame) in ascending order as ft_dtw writes them; path_len [B]; P_b = min(max(path_len[b],
+ * 1), P); cells at and behind P_b are not read.  i_c is clamped to 0 ..= (FT_PSOLA_MAX_SAMPLES - 1) / hop, j_c to 0 ..= P - 1.
+ *   J_b = j_{P_b - 1} + 1;  lo_j / hi_j = the i of the first / last cell of reference frame j (cell c is the first of its j iff
+ *   c = 0 or j_{c-1} != j_c, the last iff c = P_b - 1 or j_{c+1} != j_c: one plain store each, no atomics; a j no cell names
+ *   has lo_j = hi_j = 0, which no path of ft_dtw leaves);   mid_j = 128 hop (lo_j + hi_j)   (the middle of the matched source
+ *   frames, in 1 / Q sample);   tmap[u] = (sum over d = -w ..= w of mid[min(max(u + d, 0), J_b - 1)]) / (2 w + 1) for 0 <= u < TM,
+ *   in 64 bits, truncating.  tmap [B][TM] is nondecreasing wherever j_c does not descend and i_c does not either.
+ * FT_EINVAL: a NULL pointer, B, P, TM or hop < 1, B > 65535, hop > FT_PSOLA_MAX_SAMPLES, w outside 0 ..= FT_PSOLA_MAX_SMOOTH.
+ * FT_EUNSUPPORTED: P > FT_PSOLA_MAX_PATH (mid[] lives in LDS).
+ * Measured: profiles/prosody_warp_prof.txt.  tests/prosody_warp_ref.py replays both bit for bit. */
+#define FT_PSOLA_MAX_PATH 4096
+#define FT_PSOLA_MAX_SMOOTH 32
+int ft_psola_marks_warp(const float* f0, int64_t f0_stride_b, int64_t f0_stride_t, const float* ratio, int64_t ratio_stride_b,
+                        int64_t ratio_stride_t, const int32_t* n_samples, const int32_t* n_out_in, const int32_t* tmap,
+                        int32_t* analysis, int32_t* n_analysis, int32_t* synthesis, int32_t* source, int32_t* half,
+                        int32_t* n_synthesis, int32_t* n_out, int B, int N, int N_out, int T, int RT, int TM, int hop, int hop_out,
+                        int ratio_axis, int KA, int KS, float sr256, int unvoiced_period, void* stream);
+int ft_psola_time_map(const int32_t* path, const int32_t* path_len, int32_t* tmap, int B, int P, int TM, int hop, int w,
+                      void* stream);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

@@ -45,6 +45,13 @@ class GemmImgPlan(C.Structure):
     _fields_ = [(n, _i) for n in ("tile_rows", "stage_k", "gather", "atomics", "det", "splits", "chunk_w")]
 
 
+class GemmImgGroupPlan(C.Structure):
+    _fields_ = [(n, _i) for n in ("tile_rows", "splits", "ksteps", "atomics", "launch", "unit0", "tiles")]
+
+
+GEMM_GROUP_MAX = 48        # problems one ft_gemm_img_group call takes
+
+
 class LstmFwdRole(C.Structure):
     _fields_ = [("gx", _p), ("lens", _p), ("y", _p), ("ldy", _l), ("gates", _p), ("cell", _p), ("wimg", _p), ("state_h", _p), ("state_c", _p),
                 ("B", C.c_int32), ("ldb", C.c_int32), ("t0", C.c_int32), ("t1", C.c_int32), ("gx16", C.c_int32)]
@@ -101,6 +108,8 @@ SIGNATURES = {
     "ft_gemm_img": ([C.POINTER(GemmImgArgs), _p], _i),
     "ft_gemm_img_split_work_bytes": ([_i, _i, _i], _sz),
     "ft_gemm_img_plan": ([C.POINTER(GemmImgArgs), C.POINTER(GemmImgPlan)], _i),
+    "ft_gemm_img_group": ([C.POINTER(GemmImgArgs), _i, _p], _i),
+    "ft_gemm_img_group_plan": ([C.POINTER(GemmImgArgs), _i, C.POINTER(GemmImgGroupPlan)], _i),
     "ft_bf16_image_split3": ([_p, _l, _l, _l, _p, _i, _p], _i),
     "ft_bf16_image_split3_im2col": ([_p, _p, _i, _i, _i, _i, _p, _p], _i),
     "ft_bf16_image_split3_im2col_f16": ([_p, _p, _i, _i, _i, _i, _p, _p], _i),
@@ -244,7 +253,7 @@ SIGNATURES = {
 MIXTURE_MAX_C = 64         # FT_MIXTURE_MAX_C
 
 # fp16-operand twins (include/flowtron_hip.h, end): same signatures, suffix _f16
-OP16_TWINS = ("ft_gemm", "ft_bf16_image", "ft_bf16_image_colsum", "ft_bf16_image_colsum_acc", "ft_bf16_image_rows_acc", "ft_bf16_image_rows_act_bwd_acc", "ft_gemm_img", "ft_bf16_image_rows", "ft_bf16_image_rows_into", "ft_bf16_image_rows_act_bwd", "ft_img_gemv_rows", "ft_img_gemv_rows_bwd", "ft_lstm_seq_fwd", "ft_lstm_seq_bwd",
+OP16_TWINS = ("ft_gemm", "ft_bf16_image", "ft_bf16_image_colsum", "ft_bf16_image_colsum_acc", "ft_bf16_image_rows_acc", "ft_bf16_image_rows_act_bwd_acc", "ft_gemm_img", "ft_gemm_img_group", "ft_bf16_image_rows", "ft_bf16_image_rows_into", "ft_bf16_image_rows_act_bwd", "ft_img_gemv_rows", "ft_img_gemv_rows_bwd", "ft_lstm_seq_fwd", "ft_lstm_seq_bwd",
               "ft_lstm_persist_bwd", "ft_lstm_persist_bwd_img", "ft_lstm_roles_prepare_fwd", "ft_lstm_roles_prepare_bwd", "ft_lstm_roles_fwd", "ft_lstm_roles_bwd", "ft_lstm2_seq_fwd", "ft_lstm2_seq_bwd",
               "ft_lstm_bidir_seq_fwd", "ft_lstm_bidir_seq_bwd", "ft_bilstm_persist_fwd", "ft_bilstm_persist_bwd")
 for _n in OP16_TWINS:

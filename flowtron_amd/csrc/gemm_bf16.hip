@@ -432,8 +432,11 @@ struct Operand64 {
 // 32-wide sub-stages side by side); t0 / t1 / ksteps keep counting 32-wide steps (t0 even).  SB: a single 32 KiB LDS buffer, 4
 // workgroups per CU (with two buffers the stage is 64 KiB and only 2 workgroups fit a CU: slower than 32-wide stages at K = 1024)
 // GA: the A operand's rows are gathered through p.a_rows (compact == 1; the single-buffer form with a k-contiguous A only)
+// The body is a device function of (parameters, tile index, k-slice, number of k-slices): gemm_bf16_k runs it on blockIdx / gridDim,
+// gemm_bf16_group_k on the (problem, tile, slice) its unit index stands for.  plain (SPLIT only): the slice is the problem's only one
+// and nothing else in the launch writes its C, so the epilogue adds with a load and a store instead of atomics.
 template <bool AKM, bool BKM, bool SPLIT, int RTA, int KS = 32, bool SB = false, bool GA = false>
-__global__ __launch_bounds__(256, SB ? 4 : (RTA == 256 || KS == 64) ? 2 : 4) void gemm_bf16_k(BfP p) {
+__device__ __forceinline__ void gemm_bf16_body(const BfP& p, int tile, const int slice, const int nslices, const bool plain) {
     static_assert(!SB || (KS == 64 && RTA == 128 && !SPLIT), "single-buffer form: 128 x 128 x 64 store kernels");
     static_assert(!GA || (SB && !AKM), "row gather: the single-buffer form, k-contiguous A");
     constexpr int KQ = KS / 32;                        // MFMA k-steps per stage
@@ -443,8 +446,7 @@ __global__ __launch_bounds__(256, SB ? 4 : (RTA == 256 || KS == 64) ? 2 : 4) voi
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 15, kg = lane >> 4;
-    int tile = blockIdx.x;
-    int t0 = blockIdx.y * p.ksteps;
+    int t0 = slice * p.ksteps;
     int t1 = (t0 + p.ksteps < p.nk) ? t0 + p.ksteps : p.nk;
     int rows_lim = p.M, gy = p.gy;
     if (p.compact) {
@@ -462,8 +464,8 @@ __global__ __launch_bounds__(256, SB ? 4 : (RTA == 256 || KS == 64) ? 2 : 4) voi
                 // the k-slices divide the rows the batch HAS, not the capacity the host sized the grid for: every workgroup of
                 // the launch gets the same share of the reduction (the host's even split of the capacity left ~30 % of the slices
                 // empty and one partial -- the workgroups of a tile then finished a slice apart)
-                const int ks = (nk_eff + (int)gridDim.y - 1) / (int)gridDim.y;
-                t0 = blockIdx.y * ks;
+                const int ks = (nk_eff + nslices - 1) / nslices;
+                t0 = slice * ks;
                 t1 = t0 + ks < nk_eff ? t0 + ks : nk_eff;
                 if (t0 >= t1) return;
             } else t1 = t1 < nk_eff ? t1 : nk_eff;
@@ -611,8 +613,10 @@ __global__ __launch_bounds__(256, SB ? 4 : (RTA == 256 || KS == 64) ? 2 : 4) voi
                     const int col = n0 + wn * 64 + j * 16 + li;
                     if (col >= p.N) continue;
                     float v = p.alpha * acc[i][j][r];
-                    if (p.bias && blockIdx.y == 0) v += p.bias[col];
-                    atomicAdd(p.C + (long)row * p.ldc + col, v);
+                    if (p.bias && slice == 0) v += p.bias[col];
+                    float* cp = p.C + (long)row * p.ldc + col;
+                    if (plain) *cp = p.beta != 0.f ? *cp + v : v;       // (16 lanes = 64 consecutive bytes of a row)
+                    else atomicAdd(cp, v);
                 }
             }
         return;
@@ -628,7 +632,7 @@ __global__ __launch_bounds__(256, SB ? 4 : (RTA == 256 || KS == 64) ? 2 : 4) voi
         for (int j = 0; j < 4; ++j) {
             const int col = n0 + wn * 64 + j * 16 + kg * 4;
             if (col >= p.N) continue;
-            float* cp = p.C + (size_t)blockIdx.y * p.c_slice + (long)row * p.ldc + col;
+            float* cp = p.C + (size_t)slice * p.c_slice + (long)row * p.ldc + col;
             float v[4] = {p.alpha * acc[i][j][0], p.alpha * acc[i][j][1], p.alpha * acc[i][j][2], p.alpha * acc[i][j][3]};
             const int nv = (p.N - col < 4) ? p.N - col : 4;
             const bool full = vec && nv == 4;
@@ -653,6 +657,59 @@ __global__ __launch_bounds__(256, SB ? 4 : (RTA == 256 || KS == 64) ? 2 : 4) voi
             else for (int r = 0; r < nv; ++r) cp[r] = v[r];
         }
     }
+}
+
+template <bool AKM, bool BKM, bool SPLIT, int RTA, int KS = 32, bool SB = false, bool GA = false>
+__global__ __launch_bounds__(256, SB ? 4 : (RTA == 256 || KS == 64) ? 2 : 4) void gemm_bf16_k(BfP p) {
+    gemm_bf16_body<AKM, BKM, SPLIT, RTA, KS, SB, GA>(p, blockIdx.x, blockIdx.y, gridDim.y, false);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// grouped weight-gradient GEMMs (ft_gemm_img_group): up to GROUP_MAX problems dW = dY^T X (both operands k-major) in ONE grid.
+// A launch of the atomic split-K kernel fills the workgroup slots of the chip once, whatever its shape, and ends with every workgroup
+// pushing its partial tile through fp32 atomics at the same moment -- a fixed cost of ~34 us per launch, 31 times per training step.
+// Nothing in a backward pass reads a weight gradient, so these GEMMs can wait for each other and share a grid: a unit of the grid is one
+// (problem, tile, k-slice), the planner (plan_group) gives the units of a launch near-equal reduction lengths, the longest first, and
+// a problem that needs a single slice and shares its C with no other leaves through plain stores.
+// The table travels by value in the kernel arguments (as ImgTable does); a workgroup finds its problem by a binary search over the
+// prefix sums of the unit counts -- scalar code -- and runs gemm_bf16_k's own body.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int GROUP_MAX = 48;
+constexpr int GROUP_PLAIN = 1 << 8, GROUP_BETA1 = 1 << 9, GROUP_COMPACT = 1 << 10, GROUP_SHIFT = 12;
+struct GroupTable {
+    const unsigned short* A[GROUP_MAX]; const unsigned short* B[GROUP_MAX]; float* C[GROUP_MAX]; const float* bias[GROUP_MAX];
+    const int* rows_dev[GROUP_MAX];
+    float alpha[GROUP_MAX];
+    int M[GROUP_MAX], N[GROUP_MAX], nk[GROUP_MAX], lda[GROUP_MAX], ldb[GROUP_MAX], ldc[GROUP_MAX];
+    int how[GROUP_MAX];                     // k-slices | GROUP_PLAIN | GROUP_BETA1 | GROUP_COMPACT | k_shift << GROUP_SHIFT
+    int unit0[GROUP_MAX + 1];               // first unit of problem d; unit0[n] = the grid
+    int n;
+};
+static_assert(sizeof(GroupTable) <= 3800, "the table must fit the kernel-argument segment (4 KiB with the hidden arguments)");
+
+template <int RTA>
+__global__ __launch_bounds__(256, RTA == 256 ? 2 : 4) void gemm_bf16_group_k(GroupTable t) {
+    const int u = blockIdx.x;
+    int d = 0, hi = t.n;
+    while (hi - d > 1) {                                                         // (uniform: scalar loads of the kernel arguments)
+        const int mid = (d + hi) >> 1;
+        if (u >= t.unit0[mid]) d = mid; else hi = mid;
+    }
+    const int how = t.how[d], splits = how & 0xff;
+    BfP p;
+    p.A = t.A[d]; p.B = t.B[d]; p.C = t.C[d]; p.bias = t.bias[d];
+    p.M = t.M[d]; p.N = t.N[d]; p.nk = t.nk[d];
+    p.lda = t.lda[d]; p.ldb = t.ldb[d]; p.ldc = t.ldc[d];
+    p.alpha = t.alpha[d]; p.beta = (how & GROUP_BETA1) ? 1.f : 0.f;
+    p.act = FT_ACT_NONE;
+    p.gx = (p.N + TB - 1) / TB; p.gy = (p.M + RTA - 1) / RTA;
+    p.splits = splits; p.ksteps = (p.nk + splits - 1) / splits;
+    p.vec_c = 0;
+    p.rowmap = nullptr; p.rows_dev = t.rows_dev[d]; p.compact = (how & GROUP_COMPACT) ? 2 : 0; p.k_shift = how >> GROUP_SHIFT;
+    p.chunk_w = 0; p.r1row = nullptr; p.r1col = nullptr; p.c_slice = 0; p.c16 = 0; p.a_rows = nullptr;
+    const int local = u - t.unit0[d], tiles = p.gx * p.gy;
+    const int slice = local / tiles;                                            // slice-major: the slices of a tile are `tiles` units apart
+    gemm_bf16_body<true, true, true, RTA>(p, local - slice * tiles, slice, splits, (how & GROUP_PLAIN) != 0);
 }
 
 // (Rounds 3-6 also carried a 256 x 256 x 64 tile for the k-contiguous x k-contiguous GEMMs with many tiles and a long reduction: 8 waves,
@@ -855,6 +912,129 @@ int check_img_args(const ft_gemm_img_args* a, const char* who) {
     return FT_OK;
 }
 #undef IMG_CHECK_ARG
+
+// ---- the group planner: a pure host function of the problems' shapes, flags and C addresses -------------------------------------
+// Tile height: the 256-row tile where M has at least two of them (its slots are filled by the group, not by one problem's slices,
+// so plan_slices' fill condition falls away); one launch per tile height.  Slices: every problem of a launch is cut into pieces of
+// about one target length Lt (s = ceil(nk / Lt), at most K / 512 -- a slice keeps 16 k-steps -- and 64; K < 2048 or no
+// FT_GEMM_SPLITK: one).  Lt is the candidate nk_max / j that minimises   rounds x longest slice + E x units / slots   in k-steps:
+// the units run in rounds of the launch's workgroup slots (512 of the tall tile, 1024 of the short one), and each unit pays the
+// epilogue of one partial tile, E = 32 k-steps per full round (the ~34 us per round of profiles/r06_gemm_split_sweep.log at ~1 us
+// per k-step).  Ties go to the fewer slices.  Order: problems by slice length, longest first, so the last round ends on short units.
+// plain: one slice, and C overlaps no other problem's C (same ldc and disjoint column windows of one matrix do not overlap).
+constexpr double GROUP_EPILOGUE_KSTEPS = 32.0;
+struct GroupProb { int big, gx, gy, tiles, nk, smax, s, ks, plain, launch, unit0; };
+
+bool c_overlap(const ft_gemm_img_args& a, const ft_gemm_img_args& b) {
+    const float* a0 = a.C; const float* a1 = a.C + (size_t)(a.M - 1) * a.ldc + a.N;
+    const float* b0 = b.C; const float* b1 = b.C + (size_t)(b.M - 1) * b.ldc + b.N;
+    if (a1 <= b0 || b1 <= a0) return false;
+    if (a.ldc == b.ldc) {                                      // column windows of rows of one stride
+        const ft_gemm_img_args& lo = a0 <= b0 ? a : b; const ft_gemm_img_args& hi = a0 <= b0 ? b : a;
+        const long c = (long)((hi.C - lo.C) % lo.ldc);        // hi's first column, counted from lo's
+        if (c >= lo.N && c + hi.N <= lo.ldc) return false;
+    }
+    return true;
+}
+
+int plan_group(const ft_gemm_img_args* a, int n, GroupProb* g, int (*order)[GROUP_MAX], int* cnt, const char* who) {
+    if (!a || n < 1 || n > GROUP_MAX) return ft_fail(FT_EINVAL, "%s: 1 to %d problems", who, GROUP_MAX);
+    for (int i = 0; i < n; ++i) {
+        if (const int rc = check_img_args(a + i, who)) return rc;
+        const ft_gemm_img_args& q = a[i];
+        if (!(q.a_kmajor == 1 && q.b_kmajor == 1 && q.act == FT_ACT_NONE && (q.beta == 0.f || q.beta == 1.f) && q.compact != 1 &&
+              !q.r1_row && !q.a_rows && !(q.flags & (FT_GEMM_SPLITK_DET | FT_GEMM_C16)) && q.lda < (1ll << 31) && q.ldb < (1ll << 31) &&
+              q.ldc >= q.N && q.ldc < (1ll << 31) && q.k_shift < (1 << (31 - GROUP_SHIFT))))
+            return ft_fail(FT_EINVAL, "%s: problem %d is not a weight-gradient GEMM (both operands k-major, no activation, beta 0 or 1, "
+                                      "compact 0 or 2, no rank-1 term, row list, deterministic split or 16-bit C)", who, i);
+        GroupProb& p = g[i];
+        p.big = q.M >= 512;
+        p.gx = cdiv(q.N, TB); p.gy = cdiv(q.M, p.big ? 256 : TB); p.tiles = p.gx * p.gy;
+        p.nk = cdiv(q.K, 32);
+        p.smax = ((q.flags & FT_GEMM_SPLITK) && q.K >= 2048) ? (q.K / 512 < 64 ? q.K / 512 : 64) : 1;
+        p.launch = p.big ? 0 : 1;
+    }
+    for (int c = 0; c < 2; ++c) {
+        int* ord = order[c];
+        int m = 0, nkmax = 1;
+        for (int i = 0; i < n; ++i) if (g[i].launch == c) { ord[m++] = i; if (g[i].nk > nkmax) nkmax = g[i].nk; }
+        cnt[c] = m;
+        if (!m) continue;
+        const long slots = c == 0 ? 512 : 1024;
+        double best = 0.0; int best_lt = 0, prev_lt = 0;
+        for (int j = 1; j <= 64; ++j) {
+            const int lt = cdiv(nkmax, j);
+            if (lt == prev_lt) continue;
+            prev_lt = lt;
+            long units = 0; int longest = 0;
+            for (int k = 0; k < m; ++k) {
+                const GroupProb& p = g[ord[k]];
+                int sl = cdiv(p.nk, lt);
+                sl = sl > p.smax ? p.smax : sl;
+                const int ks = cdiv(p.nk, sl);
+                units += (long)p.tiles * cdiv(p.nk, ks);
+                if (ks > longest) longest = ks;
+            }
+            const double cost = (double)cdiv(units, slots) * longest + GROUP_EPILOGUE_KSTEPS * (double)units / (double)slots;
+            if (best_lt == 0 || cost < best) { best = cost; best_lt = lt; }
+            if (lt == 1) break;
+        }
+        for (int k = 0; k < m; ++k) {
+            GroupProb& p = g[ord[k]];
+            int sl = cdiv(p.nk, best_lt);
+            sl = sl > p.smax ? p.smax : sl;
+            p.ks = cdiv(p.nk, sl);
+            p.s = cdiv(p.nk, p.ks);
+            p.ks = cdiv(p.nk, p.s);                            // (what the kernel derives from s)
+        }
+        for (int k = 1; k < m; ++k) {                          // longest slices first (stable)
+            const int v = ord[k];
+            int h = k;
+            while (h > 0 && g[ord[h - 1]].ks < g[v].ks) { ord[h] = ord[h - 1]; --h; }
+            ord[h] = v;
+        }
+        int u = 0;
+        for (int k = 0; k < m; ++k) { g[ord[k]].unit0 = u; u += g[ord[k]].tiles * g[ord[k]].s; }
+    }
+    for (int i = 0; i < n; ++i) {
+        bool alone = true;
+        for (int k = 0; k < n && alone; ++k) if (k != i && c_overlap(a[i], a[k])) alone = false;
+        g[i].plain = (g[i].s == 1 && alone) ? 1 : 0;
+    }
+    return FT_OK;
+}
+
+int run_group(const ft_gemm_img_args* a, int n, hipStream_t st, const char* who) {
+    GroupProb g[GROUP_MAX];
+    int order[2][GROUP_MAX], cnt[2];
+    if (const int rc = plan_group(a, n, g, order, cnt, who)) return rc;
+    for (int i = 0; i < n; ++i)                                // the atomic epilogue adds: a beta = 0 output starts at zero
+        if (!g[i].plain && a[i].beta == 0.f)
+            FT_CHECK_HIP(hipMemset2DAsync(a[i].C, sizeof(float) * a[i].ldc, 0, sizeof(float) * a[i].N, a[i].M, st));
+    for (int c = 0; c < 2; ++c) {
+        if (!cnt[c]) continue;
+        GroupTable t{};
+        t.n = cnt[c];
+        int units = 0;
+        for (int k = 0; k < cnt[c]; ++k) {
+            const int i = order[c][k];
+            const ft_gemm_img_args& q = a[i];
+            t.A[k] = reinterpret_cast<const unsigned short*>(q.A); t.B[k] = reinterpret_cast<const unsigned short*>(q.B);
+            t.C[k] = q.C; t.bias[k] = q.bias; t.rows_dev[k] = q.compact == 2 ? q.rows_dev : nullptr;
+            t.alpha[k] = q.alpha;
+            t.M[k] = q.M; t.N[k] = q.N; t.nk[k] = g[i].nk; t.lda[k] = (int)q.lda; t.ldb[k] = (int)q.ldb; t.ldc[k] = (int)q.ldc;
+            t.how[k] = g[i].s | (g[i].plain ? GROUP_PLAIN : 0) | (q.beta != 0.f ? GROUP_BETA1 : 0) | (q.compact == 2 ? GROUP_COMPACT : 0) |
+                       (q.k_shift << GROUP_SHIFT);
+            t.unit0[k] = g[i].unit0;
+            units = g[i].unit0 + g[i].tiles * g[i].s;
+        }
+        for (int k = cnt[c]; k <= GROUP_MAX; ++k) t.unit0[k] = units;
+        if (c == 0) hipLaunchKernelGGL((gemm_bf16_group_k<256>), dim3(units), dim3(256), 0, st, t);
+        else hipLaunchKernelGGL((gemm_bf16_group_k<128>), dim3(units), dim3(256), 0, st, t);
+    }
+    FT_CHECK_LAUNCH();
+    return FT_OK;
+}
 
 bool qualifies(const ft_gemm_args* a) {
     return a->mode == FT_OP16 && a->batch == 1 && a->M >= 32 && a->N >= 32 && a->K >= 16 &&
@@ -1123,6 +1303,30 @@ extern "C" int FT_OPNAME(ft_gemm_img)(const ft_gemm_img_args* a, void* stream) {
                       a->ldb, a->b_kmajor, a->C, a->ldc, a->bias, a->M, a->N, a->K, a->alpha, a->beta, a->act, a->flags,
                       reinterpret_cast<hipStream_t>(stream), a->rowmap, a->rows_dev, a->compact, a->k_shift, a->r1_row, a->r1_col,
                       reinterpret_cast<float*>(a->split_work), a->split_work_bytes, a->a_rows);
+}
+
+#if FT_OPFMT == 0
+// what ft_gemm_img_group(probs, n) would launch (plan_group, the launcher's own decision); format-independent
+extern "C" int ft_gemm_img_group_plan(const ft_gemm_img_args* probs, int n, ft_gemm_img_group_plan_t* out) {
+    FT_CHECK_ARG(out != nullptr);
+    GroupProb g[GROUP_MAX];
+    int order[2][GROUP_MAX], cnt[2];
+    if (const int rc = plan_group(probs, n, g, order, cnt, __func__)) return rc;
+    for (int i = 0; i < n; ++i) {
+        out[i].tile_rows = g[i].big ? 256 : TB;
+        out[i].splits = g[i].s;
+        out[i].ksteps = g[i].ks;
+        out[i].atomics = g[i].plain ? 0 : 1;
+        out[i].launch = (g[i].launch == 1 && cnt[0] == 0) ? 0 : g[i].launch;
+        out[i].unit0 = g[i].unit0;
+        out[i].tiles = g[i].tiles;
+    }
+    return FT_OK;
+}
+#endif
+
+extern "C" int FT_OPNAME(ft_gemm_img_group)(const ft_gemm_img_args* probs, int n, void* stream) {
+    return run_group(probs, n, reinterpret_cast<hipStream_t>(stream), __func__);
 }
 
 // compact image: image row i = source row rowmap[i] (i < *rows_dev; -1 = zero row); buffer sized for cap_rows

@@ -342,6 +342,9 @@ def apply_gradient_allreduce(module):
             return
         state["launched"][bi] = True
         _, lo, hi, idx = buckets[bi]
+        if on_gpu:
+            from .ops import flush_weight_grads
+            flush_weight_grads()                                 # the bucket's deferred weight-gradient GEMMs run before it is reduced
         arena.adopt_stray_grads(copy=True, only=idx)
         if on_gpu:
             from .optim import poison_from_status
@@ -351,6 +354,9 @@ def apply_gradient_allreduce(module):
 
     def finish_backward():
         state["queued"] = False
+        if on_gpu:
+            from .ops import flush_weight_grads
+            flush_weight_grads()                                 # (this callback may run before the queue's own)
         if module.needs_reduction:
             module.needs_reduction = False
             timed = module._comm_timing and on_gpu and dist.is_initialized()

@@ -353,6 +353,137 @@ def gemm_img_plan(A, a_km, a_ptr, B, b_km, b_ptr, Cm, M, N, K, ldc, **kw):
     return plan
 
 
+# Weight-gradient GEMMs of a backward pass in grouped launches (ft_gemm_img_group).  Nothing in the backward chain reads a weight
+# gradient, so the image-path dW GEMMs wait in a per-pass queue and run together: one grid per tile height instead of ~31 launches
+# that each fill the chip once and end on ~512 partial tiles of atomics.  A queued problem holds the buffers of both operand images, the row map
+# and an alias of C until it has run; every image of a pass is a fresh allocation that no later kernel writes again (the hand-off and
+# shared_image only pass references on, the pair backward's windows have all written their dgates images before its weight gradients
+# are queued), so holding the reference is all the lifetime a queued operand needs -- at the price of the images staying allocated
+# to the end of the pass.
+# The queue runs (a) from an engine callback queued with the first deferred problem of the pass, (b) when the table is full, (c) from
+# flush_weight_grads(), which whoever reads gradients before the pass ends calls first (dist: a bucket's all-reduce).
+# A problem is deferred only where the tensor it writes is the one autograd will adopt as .grad without reading it: the weight is a
+# leaf (or a reshape of one) without a gradient yet, without tensor hooks, met for the first time in the pass, outside anomaly mode and
+# double backward.  Everything else -- and everything outside a backward pass, or with _DW_GROUP = False -- launches at once, and a
+# later gradient of a weight whose first one waits runs the queue first (_dw_other_gradient).  By construction outside this module:
+# a weight that ALSO feeds a foreign autograd node in the same pass would have its two gradients added before the queue has run.
+_DW_GROUP = True
+_DWQ = {"task": None, "items": [], "seen": {}}
+
+
+def _dw_leaf(W):
+    """the leaf whose .grad the gradient of W becomes through reshapes alone, or None where that cannot be told"""
+    if W.is_leaf:
+        return W
+    b = W._base
+    if b is not None and b.is_leaf and b.numel() == W.numel() and W.is_contiguous() and b.is_contiguous():
+        return b
+    return None
+
+
+def _dw_end_of_pass():
+    flush_weight_grads()
+    _DWQ["task"], _DWQ["seen"] = None, {}
+
+
+def _dw_pass():
+    """the queue state of the current backward pass, armed at its first use (as _handoff_put does: keyed by the engine's graph task,
+    the leftovers of a pass that raised are dropped, never launched); None outside a pass and wherever nothing is deferred"""
+    if not _DW_GROUP or torch.is_grad_enabled() or torch.is_anomaly_enabled():
+        return None
+    gt = _current_graph_task()
+    if gt == -1:
+        return None
+    q = _DWQ
+    if q["task"] != gt:
+        try:
+            torch.autograd.Variable._execution_engine.queue_callback(_dw_end_of_pass)
+        except RuntimeError:
+            return None
+        q["task"], q["items"], q["seen"] = gt, [], {}
+    return q
+
+
+def _dw_deferrable(W, dW):
+    """whether this weight-gradient GEMM may wait for the flush"""
+    q = _dw_pass()
+    if q is None or W is None:
+        return False
+    leaf = _dw_leaf(W)
+    if leaf is None or not leaf.requires_grad or leaf.grad is not None or leaf._backward_hooks:
+        return False
+    first = q["seen"].setdefault(id(leaf), dW.data_ptr())
+    if first != dW.data_ptr():
+        flush_weight_grads()            # a second gradient of one weight in the pass: the engine adds the two, so the first must be there
+        return False
+    return True
+
+
+def _dw_other_gradient(W):
+    """A gradient of W is about to be produced OUTSIDE the queue (an fp32-staging GEMM, a scatter-add, zeros).  A weight may be used
+    more than once in a pass -- a batch wider than the recurrence kernels runs its layers per batch chunk, and a chunk may be too
+    small for the image path -- and the engine adds the gradients of one weight as soon as the later one arrives: one that still
+    waits in the queue is written first, and one that comes after this one will not wait (address 0 matches no C).  Every other
+    producer of a gradient for a weight that can also reach weight_grad_gemm (LinearFn and the recurrences) calls this."""
+    q = _dw_pass()
+    leaf = _dw_leaf(W) if (q is not None and W is not None) else None
+    if leaf is None:
+        return
+    if id(leaf) in q["seen"]:
+        flush_weight_grads()
+    q["seen"][id(leaf)] = 0
+
+
+def weight_grad_gemm(W, dW, A, a_ptr, B, b_ptr, Cm, M, N, K, ldc, **kw):
+    """The image-path weight-gradient GEMM Cm (+)= A^T B (both images k-major, gemm_img's arguments with splitk = True), Cm = dW or a
+    column window of it, dW = the gradient the node returns for the weight W.  Inside a backward pass the call joins the pass's queue
+    (see above) and runs with the others in ft_gemm_img_group; else it is gemm_img itself."""
+    if not _dw_deferrable(W, dW):
+        gemm_img(A, 1, a_ptr, B, 1, b_ptr, Cm, M, N, K, ldc, splitk=True, **kw)
+        return
+    a, _work = _gemm_img_args(A, 1, a_ptr, B, 1, b_ptr, Cm, M, N, K, ldc, splitk=True, **kw)
+    # (the images' buffers, not the images, and an alias of C, not C: autograd adopts a returned gradient -- C here, an image's column
+    #  sums as a bias gradient -- without a copy only while nobody else holds that tensor)
+    _DWQ["items"].append((a, A.fmt, L.stream(), Cm.device, (A.buf, B.buf, Cm.detach(), kw.get("rowmap"), kw.get("bias"))))
+    if len(_DWQ["items"]) >= L.GEMM_GROUP_MAX:
+        flush_weight_grads()
+
+
+def gemm_img_group(arg_list, fmt, stream=None):
+    """ft_gemm_img_group over a list of ft_gemm_img_args (at most L.GEMM_GROUP_MAX) of operand format fmt"""
+    arr = (L.GemmImgArgs * len(arg_list))(*arg_list)
+    L.check(L.op16("ft_gemm_img_group", fmt)(arr, len(arg_list), L.stream() if stream is None else stream), "ft_gemm_img_group")
+
+
+def gemm_img_group_plan(arg_list):
+    """what gemm_img_group would launch: one L.GemmImgGroupPlan per problem (ft_gemm_img_group_plan; nothing is launched)"""
+    arr = (L.GemmImgArgs * len(arg_list))(*arg_list)
+    out = (L.GemmImgGroupPlan * len(arg_list))()
+    L.check(L.lib().ft_gemm_img_group_plan(arr, len(arg_list), out), "ft_gemm_img_group_plan")
+    return list(out)
+
+
+def _dw_run(batch):
+    """one ft_gemm_img_group call over queue items (args, format, stream, device, kept references) of one format, stream and device"""
+    with torch.cuda.device(batch[0][3]):
+        gemm_img_group([it[0] for it in batch], batch[0][1], batch[0][2])
+
+
+def flush_weight_grads():
+    """run every weight-gradient GEMM the current backward pass has deferred; after it the gradients produced so far are complete.
+    Call it before reading a gradient inside a pass (a hook, a collective over finished buckets)."""
+    items, _DWQ["items"] = _DWQ["items"], []
+    gt = _current_graph_task()
+    if gt != -1 and gt != _DWQ["task"]:
+        return                          # leftovers of a pass that raised, met inside a later pass: dropped, never launched
+    while items:
+        fmt, st, dev = items[0][1:4]
+        batch = [it for it in items if it[1:4] == (fmt, st, dev)][:L.GEMM_GROUP_MAX]
+        taken = set(id(it) for it in batch)
+        items = [it for it in items if id(it) not in taken]
+        _dw_run(batch)
+
+
 # hand-off of an output-gradient image between two autograd nodes of the SAME backward pass (the LSTM backward builds the
 # image of dgates for its own dW_hh GEMM; the input projection's LinearFn.backward receives that very tensor as dy).
 # Keyed by (device, data_ptr, shape); cleared by an engine callback at the end of the pass, so an address can never match stale data.
@@ -699,6 +830,8 @@ class LinearFn(torch.autograd.Function):
             dpre = dy
         dW = None
         if ctx.needs_input_grad[0]:
+            if ctx.imgs is None:
+                _dw_other_gradient(W)
             dW = weight_grad_out(W) if ctx.imgs is not None else torch.empty_like(W)      # (image path: split-K with beta = 1)
         db = None
         dxs = []
@@ -738,12 +871,12 @@ class LinearFn(torch.autograd.Function):
                 dxs.append(None)
             if dW is not None and ctx.cat:
                 if i == 0:      # one split-K GEMM over the concatenated image: dW[n, :] = sum_r dpre[r,n] [x_0 | x_1][r, :]
-                    gemm_img(d_img, 1, d_img.ptr(), x_imgs[0], 1, x_imgs[0].ptr(), dW, N, Ktot, mrows, Ktot, beta=1.0, splitk=True, rowmap=rowmap, compact=2)
+                    weight_grad_gemm(W, dW, d_img, d_img.ptr(), x_imgs[0], x_imgs[0].ptr(), dW, N, Ktot, mrows, Ktot, beta=1.0, rowmap=rowmap, compact=2)
             elif dW is not None:
                 # dW[n, off+k] = sum_r dpre[r,n] x[r,k]
                 if imgs is not None:
-                    gemm_img(d_img, 1, d_img.ptr(), x_imgs[i], 1, x_imgs[i].ptr(), dW[:, off:], N, K, mrows, Ktot, beta=1.0, splitk=True,
-                             rowmap=rowmap, compact=2)
+                    weight_grad_gemm(W, dW, d_img, d_img.ptr(), x_imgs[i], x_imgs[i].ptr(), dW[:, off:], N, K, mrows, Ktot, beta=1.0,
+                                     rowmap=rowmap, compact=2)
                     if rowmap is not None:
                         _handoff_put_x(x, x_imgs[i])
                 else:
@@ -845,7 +978,7 @@ class LinearGateFn(torch.autograd.Function):
         dW = None
         if ctx.needs_input_grad[0]:
             dW = weight_grad_out(W)
-            gemm_img(d_img, 1, d_img.ptr(), x_cat, 1, x_cat.ptr(), dW, N, Ktot, rowmap.cap, Ktot, beta=1.0, splitk=True, rowmap=rowmap, compact=2)
+            weight_grad_gemm(W, dW, d_img, d_img.ptr(), x_cat, x_cat.ptr(), dW, N, Ktot, rowmap.cap, Ktot, beta=1.0, rowmap=rowmap, compact=2)
         dWg = dbg = None
         if dgate is not None and (ctx.needs_input_grad[2] or (ctx.has_gbias and ctx.needs_input_grad[3])):
             acc = zeroed((Ktot + 1,), W.device)
@@ -886,6 +1019,7 @@ class EmbeddingFn(torch.autograd.Function):
     def backward(ctx, dout):
         ids, W = ctx.saved_tensors
         dout = _c(dout)
+        _dw_other_gradient(W)
         dW = weight_grad_out(W)                     # zero-filled; the scatter-add accumulates
         if ctx.run_stride > 0:
             L.check(L.lib().ft_embedding_bwd_runs(L.ptr(ids), L.ptr(dout), L.ptr(dW), ids.numel(), W.shape[1], W.shape[1], ctx.run_stride,
@@ -1540,10 +1674,10 @@ def _leave_dgates(dgx, d_img, shape, gx_dtype):
     return dgx
 
 
-def _compact_dw(d_img, y_img, dW, shift):
+def _compact_dw(W, d_img, y_img, dW, shift):
     """dW += dgates^T y over the compact rows of the images' RowMap (split-K); shift 1 for a recurrent weight: dgates_t meets h_{t-1}"""
     rm, H = d_img.rowmap, y_img.cols
-    gemm_img(d_img, 1, d_img.ptr(shift), y_img, 1, y_img.ptr(0), dW, d_img.cols, H, rm.cap, H, beta=1.0, splitk=True, rowmap=rm, compact=2, k_shift=shift)
+    weight_grad_gemm(W, dW, d_img, d_img.ptr(shift), y_img, y_img.ptr(0), dW, d_img.cols, H, rm.cap, H, beta=1.0, rowmap=rm, compact=2, k_shift=shift)
 
 
 def _pair_weight_grads(ctx, saved, d_img1, d_img0):
@@ -1556,9 +1690,9 @@ def _pair_weight_grads(ctx, saved, d_img1, d_img0):
     y1_img = y_image(y1, T * B, H, ctx.mode, rm) if need[5] else None
     jobs = [(need[5], w_hh1, d_img1, y1_img, 1), (need[2], w_ih1, d_img1, y0_img, 0), (need[1], w_hh0, d_img0, y0_img, 1)]
     outs = [weight_grad_out(w) if on else None for on, w, _, _, _ in jobs]
-    for dW, (on, _, d, y, shift) in zip(outs, jobs):
+    for dW, (on, w, d, y, shift) in zip(outs, jobs):
         if on:
-            _compact_dw(d, y, dW, shift)
+            _compact_dw(w, d, y, dW, shift)
     return outs
 
 
@@ -1741,6 +1875,8 @@ class LSTMSeqFn(torch.autograd.Function):
         dgx, d_img = produce(ctx, saved, dy)           # (fp32 rows | None, compact image | None): no rows = the image is the only form
         # dW_hh[r,j] = sum_{t,b} da_t[b,r] * h_prev(t)[b,j];  h_prev = y[t-1] (fwd) / y[t+1] (reverse)
         dW = weight_grad_out(w_hh) if ctx.needs_input_grad[1] else None
+        if dW is not None and (T <= 1 or not images_apply(ctx.mode, 4 * H, H, (T - 1) * B)):
+            _dw_other_gradient(w_hh)                    # (zeros, or the fp32-staging GEMM below)
         if dW is not None and T > 1:
             rows, rm, fwd = (T - 1) * B, ctx.rowmap, not ctx.reverse
             if not images_apply(ctx.mode, 4 * H, H, rows):
@@ -1750,11 +1886,11 @@ class LSTMSeqFn(torch.autograd.Function):
                 # dgates_t <-> h_{t-1} is a shift by ONE compact row, and the utterance boundaries multiply with a separator
                 if d_img is None:
                     d_img = Bf16Image(dgx.reshape(T * B, 4 * H), colsum=True, mode=ctx.mode, rowmap=rm)
-                _compact_dw(d_img, y_image(y, T * B, H, ctx.mode, rm), dW, 1)
+                _compact_dw(w_hh, d_img, y_image(y, T * B, H, ctx.mode, rm), dW, 1)
             else:
                 # images of dgates / outputs over all T*B rows; the one-step shift is a row offset into them
                 d_img, y_img = Bf16Image(dgx.reshape(T * B, 4 * H), colsum=True, mode=ctx.mode), shared_image(y, T * B, H, ctx.mode)
-                gemm_img(d_img, 1, d_img.ptr(B if fwd else 0), y_img, 1, y_img.ptr(0 if fwd else B), dW, 4 * H, H, rows, H, beta=1.0, splitk=True)
+                weight_grad_gemm(w_hh, dW, d_img, d_img.ptr(B if fwd else 0), y_img, y_img.ptr(0 if fwd else B), dW, 4 * H, H, rows, H, beta=1.0)
         return _leave_dgates(dgx, d_img, (T, B, 4 * H), ctx.gx_dtype), dW, None, None, None, None, None
 
 
@@ -1846,6 +1982,7 @@ class BiLSTMSeqFn(torch.autograd.Function):
         rows = (T - 1) * B
         for d in range(2):
             if ctx.needs_input_grad[2 + d]:
+                _dw_other_gradient(w_f if d == 0 else w_r)
                 dWs[d] = weight_grad_out(w_f if d == 0 else w_r)         # zero-filled: the GEMM accumulates (beta = 1)
                 if T > 1:
                     # dW_hh[r,j] = sum da_t[b,r] h_prev(t)[b,j];  h_prev = y[t-1] (forward) / y[t+1] (reverse), y row stride 2H
@@ -2358,12 +2495,14 @@ class LSTM2SeqFn(torch.autograd.Function):
             # hand-off, the dX / dW GEMMs of the layer-0 input projection
             d0, d1 = Bf16Image(dgx0.reshape(rows, 4 * H), colsum=True, mode=mode), Bf16Image(dgx1.reshape(rows, 4 * H), colsum=True, mode=mode)
             i0, i1 = Bf16Image(y0.reshape(rows, H), mode=mode), shared_image(y1, rows, H, mode)
-            gemm_img(d0, 1, d0.ptr(B), i0, 1, i0.ptr(), dW_hh0, 4 * H, H, r1, H, splitk=True)
-            gemm_img(d1, 1, d1.ptr(B), i1, 1, i1.ptr(), dW_hh1, 4 * H, H, r1, H, splitk=True)
-            gemm_img(d1, 1, d1.ptr(), i0, 1, i0.ptr(), dW_ih1, 4 * H, H, rows, H, splitk=True)
+            weight_grad_gemm(w_hh0, dW_hh0, d0, d0.ptr(B), i0, i0.ptr(), dW_hh0, 4 * H, H, r1, H)
+            weight_grad_gemm(w_hh1, dW_hh1, d1, d1.ptr(B), i1, i1.ptr(), dW_hh1, 4 * H, H, r1, H)
+            weight_grad_gemm(w_ih1, dW_ih1, d1, d1.ptr(), i0, i0.ptr(), dW_ih1, 4 * H, H, rows, H)
             _handoff_put(dgx0, d0)
             db1 = d1.colsum
         else:
+            for w in (w_hh0, w_hh1, w_ih1):
+                _dw_other_gradient(w)
             if T > 1:
                 gemm_raw(dgx0[1:], y0[:-1], dW_hh0, 4 * H, H, r1, 1, 4 * H, H, 1, H, mode=mode, splitk=True)
                 gemm_raw(dgx1[1:], y1[:-1], dW_hh1, 4 * H, H, r1, 1, 4 * H, H, 1, H, mode=mode, splitk=True)

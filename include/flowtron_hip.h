@@ -163,6 +163,19 @@ typedef struct { int tile_rows;      /* 128 | 256 */
                  int stage_k;        /* 32 | 64 (64 = single-buffer form) */
                  int gather, atomics, det, splits, chunk_w; } ft_gemm_img_plan_t;
 int ft_gemm_img_plan(const ft_gemm_img_args* a, ft_gemm_img_plan_t* out);
+/* Grouped weight-gradient GEMMs (added under ABI 15: a new entry point, nothing existing changes).  n (1 .. 48) problems, each the
+ * ft_gemm_img_args of a weight-gradient call -- a_kmajor = b_kmajor = 1, no activation, beta 0 or 1, optional bias (added once), compact
+ * 0 or 2 with rows_dev / k_shift, fp32 C of any ldc, FT_GEMM_SPLITK to allow k-slices (K >= 2048) -- run in ONE grid per tile height
+ * (256-row tiles where M >= 512, else 128): a workgroup is one (problem, tile, k-slice).  The planner cuts every problem of a launch
+ * into slices of near-equal length that fill whole rounds of the chip's workgroup slots with as few slices as that takes, longest
+ * first; a problem with ONE slice whose C overlaps no other problem's C is written with plain loads and stores, the others add with
+ * fp32 atomics (beta = 0: C is cleared first).  Anything else in a problem: FT_EINVAL, nothing is launched.  probs is a HOST array.
+ * The plan query reports, per problem in the caller's order: the tile height, the k-slices and their length in 32-wide k-steps (compact
+ * = 2: the kernel divides the rows the batch has over the slices instead), atomics (0 = plain stores), the launch (0 = first) and
+ * the problem's first unit and tile count in it: unit u of the problem is k-slice u / tiles of tile u % tiles.  No launch, no device access. */
+typedef struct { int tile_rows, splits, ksteps, atomics, launch, unit0, tiles; } ft_gemm_img_group_plan_t;
+int ft_gemm_img_group_plan(const ft_gemm_img_args* probs, int n, ft_gemm_img_group_plan_t* out);
+int ft_gemm_img_group(const ft_gemm_img_args* probs, int n, void* stream);
 size_t ft_bf16_image_bytes(int64_t rows, int64_t cols);
 int ft_bf16_image(const float* src, int64_t ld, int64_t rows, int64_t cols, void* dst, void* stream);
 /* the same image plus colsum[c] = sum_r src[r][c] in fp32 (bias gradients ride on the conversion pass of the output
@@ -1229,6 +1242,7 @@ int ft_gemm_f16(const ft_gemm_args* a, void* stream);
 int ft_bf16_image_f16(const float* src, int64_t ld, int64_t rows, int64_t cols, void* dst, void* stream);
 int ft_bf16_image_colsum_f16(const float* src, int64_t ld, int64_t rows, int64_t cols, void* dst, float* colsum, void* stream);
 int ft_gemm_img_f16(const ft_gemm_img_args* a, void* stream);
+int ft_gemm_img_group_f16(const ft_gemm_img_args* probs, int n, void* stream);
 int ft_bf16_image_rows_f16(const float* src, int64_t ld, int64_t cap_rows, int64_t cols, void* dst, float* colsum,
                            const int32_t* rowmap, const int32_t* rows_dev, void* stream);
 int ft_lstm_seq_fwd_f16(const float* gx, const float* w_hh, const int32_t* lens,

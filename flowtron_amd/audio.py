@@ -3,9 +3,11 @@ TacotronSTFT.mel_spectrogram as ONE HIP kernel (reflect pad + windowed real FFT 
 filterbank + log-compression) instead of a 1026x1024 dense-DFT conv1d.  Two kernel families share the work
 (STFT._call picks one): ft_stft_r8 / ft_istft_r8 (csrc/stft_r8.hip) at n_fft 1024 with hop <= 256, and
 ft_stft_pow2 / ft_istft_pow2 (csrc/stft_pow2.hip) at every other setting with n_fft in POW2_NFFT and
-1 <= hop <= win_length <= n_fft; both sit on csrc/stft_common.h.  Only a mel spectrogram outside both (another
-n_fft, more than 128 mel channels, a signal no longer than n_fft / 2) falls to ft_stft_mel (csrc/stft.hip:
-complex radix-2 FFT + dense filterbank).
+1 <= hop <= win_length <= n_fft; both sit on csrc/stft_common.h.  Only a mel spectrogram outside both (n_fft 64 or
+128, more than 128 mel channels, a hop above win_length) falls to ft_stft_mel (csrc/stft.hip: complex radix-2 FFT
++ dense filterbank), which takes every power-of-two n_fft from 64 to 4096 with hop <= n_fft whose frames fit its
+160 KB of LDS.  Any other n_fft, and a signal no longer than n_fft / 2 (the reflect padding needs more), is
+refused by every entry: mel_spectrogram raises.
 
 The synthesis side (audio_processing.py:7-75, 237-270) is here too: STFT.inverse / STFT.forward run
 the inverse real FFT + overlap-add kernel of the setting's family, `griffin_lim` loops it with the forward
@@ -619,7 +621,11 @@ class TacotronSTFT(torch.nn.Module):
     def mel_spectrogram_ragged(self, y, n_samples, max_t=None):
         """The collated batch of the data path in one launch (ft_stft_r8_ragged / ft_stft_pow2_ragged): y [B,N] zero-padded audio on the device,
         n_samples [B] (int32, device) -> [B, n_mel_channels, max_t]; utterance b's frames t < n_samples[b] // hop + 1 equal
-        mel_spectrogram(y[b:b+1, :n_samples[b]]), later frames are zero (DataCollate's padding, data.py:215-229)."""
+        mel_spectrogram(y[b:b+1, :n_samples[b]]), later frames are zero (DataCollate's padding, data.py:215-229).
+        The lengths stay on the device, so an utterance of n_samples[b] <= n_fft / 2, which mel_spectrogram refuses, cannot be
+        refused here: its n_samples[b] // hop + 1 frames are computed under the kernel's own padding rule, one reflection at
+        each end (n < 0 -> -n, then n >= n_samples[b] -> 2 (n_samples[b] - 1) - n) and zeros where the index still falls
+        outside the utterance; the other utterances of the batch are not affected."""
         L.require_cuda(y, n_samples)
         y = y.contiguous().float()
         if self.mel_basis.device != y.device:

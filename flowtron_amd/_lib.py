@@ -231,6 +231,7 @@ SIGNATURES = {
     "ft_psola_synth": ([_p, _l, _l] + [_p] * 9 + [_i] * 5 + [_p], _i),
     "ft_psola_marks_warp": ([_p, _l, _l, _p, _l, _l] + [_p] * 10 + [_i] * 11 + [_f, _i, _p], _i),
     "ft_psola_time_map": ([_p, _p, _p, _i, _i, _i, _i, _i, _p], _i),
+    "ft_spectral_envelope": ([_p, _l, _l, _p, _p, _l, _l, _p, _p, _p, _p] + [_i] * 6 + [_f] * 4 + [_p], _i),
     "ft_attn_ctc_workspace_floats":([_i, _i, _i], _sz),
     "ft_attn_ctc_fwd": ([_p, _p, _p, _f, _p, _p, _i, _i, _i, _i, _p], _i),
     "ft_attn_ctc_bwd": ([_p, _p, _p, _f, _p, _p, _p, _i, _i, _i, _i, _p], _i),

@@ -7,6 +7,8 @@ another length, in dB (additive: the reference has no metric of its own; csrc/dt
     cep = mel_cepstra(mel, lens, n_coeffs=13)                                         # [B, T, K] cepstra 1 .. K (no c0)
     cost, path, path_len = dtw(cep_a, cep_b, a_lens, b_lens)                          # the warp itself, on any features
     rmse_cents, vuv_error, n_voiced = f0_distortion(f0_a, f0_b, path, path_len)       # pitch error along a path (pitch.f0)
+    mcd = envelope_cepstral_distortion(audio_a, n_a, f0_a, audio_b, n_b, f0_b)        # [B] dB on mel-cepstra of the F0-adaptive
+                                                                                      # envelope: the one to use where the pitch differs
 
 Everything runs on the device and refuses tensors on the host; lengths are lists or integer tensors, on the host or the
 device (read to the host once, as Flowtron.infer reads them)."""
@@ -155,6 +157,39 @@ def mel_cepstral_distortion(mel_a, a_lens, mel_b, b_lens, n_coeffs=13, align=Tru
     al, bl = _pair_lengths(a_lens, b_lens, B, Ta, Tb, ("a_lens", "b_lens"), not align, "align=False")
     L.require_cuda(mel_a, mel_b)
     cost, path, path_len = _dtw(_cepstra(mel_a, al, K), _cepstra(mel_b, bl, K), al, bl, not align)
+    mcd = (MCD_SCALE * cost.double() / path_len.double()).float()
+    return (mcd, path, path_len) if return_path else mcd
+
+
+def envelope_cepstral_distortion(audio_a, n_a, f0_a, audio_b, n_b, f0_b, sampling_rate=22050, hop_length=256, order=24, alpha=None,
+                                 align=True, return_path=False):
+    """Mel-cepstral distortion in dB as the papers compute it, between two batches of WAVEFORMS, pair by pair: mel-cepstra
+    1 .. order (no c0) of the F0-adaptive spectral envelope (envelope.mel_cepstra: CheapTrick, SPTK's frequency transform with
+    all-pass constant alpha, None = the customary value for the rate) of audio_a [B, Na] and audio_b [B, Nb] (fp32 on the
+    device, zero-padded), n_a / n_b their samples (lists or integer tensors, read to the host once; None: all), f0_a / f0_b
+    their pitch tracks in Hz at this hop (pitch.f0 or pitch.f0_track).  The envelope does not resolve the harmonics, so the
+    figure does not move with F0 the way mel_cepstral_distortion's does: use this one whenever the two sides differ in pitch.
+        mcd[b] = (10 / ln 10) sqrt(2) * mean over the path's cells (i, j) of || mc_a[i, 1:] - mc_b[j, 1:] ||
+    along the path of dtw() over n // hop_length + 1 frames a side (align=False: frame i with frame i, equal frame counts),
+    formed as mel_cepstral_distortion forms it; the coefficients go through dtw() as strided views of the kernel's output.
+    The frames are the F0 track's, at the STFT hop, not the 5 ms of most papers; NOT pinned against pyworld / pysptk.
+    -> mcd [B] fp32, and with return_path also (path [B, Ta + Tb - 1, 2] int32, path_len [B] int32), which f0_distortion takes."""
+    from . import envelope
+    for a, name in ((audio_a, "audio_a"), (audio_b, "audio_b")):
+        if not torch.is_tensor(a) or a.dim() != 2:
+            raise ValueError("%s must be a [B, N] tensor, got %s" % (name, tuple(a.shape) if torch.is_tensor(a) else type(a).__name__))
+    B, Na = audio_a.shape
+    Nb = audio_b.shape[1]
+    if audio_b.shape[0] != B:
+        raise ValueError("audio_a holds %d utterances and audio_b %d: one pair per utterance" % (B, audio_b.shape[0]))
+    hop = envelope._int_arg(hop_length, "hop_length", 1)
+    na = lengths_arg(n_a, "n_a", B, Na) or [Na] * B
+    nb = lengths_arg(n_b, "n_b", B, Nb) or [Nb] * B
+    al, bl = _pair_lengths([n // hop + 1 for n in na], [n // hop + 1 for n in nb], B, Na // hop + 1, Nb // hop + 1, ("n_a", "n_b"),
+                           not align, "align=False")
+    mc_a = envelope.mel_cepstra(audio_a, na, f0_a, sampling_rate, hop, order, alpha)
+    mc_b = envelope.mel_cepstra(audio_b, nb, f0_b, sampling_rate, hop, order, alpha)
+    cost, path, path_len = dtw(mc_a[:, :, 1:], mc_b[:, :, 1:], al, bl, diagonal=not align)
     mcd = (MCD_SCALE * cost.double() / path_len.double()).float()
     return (mcd, path, path_len) if return_path else mcd
 

@@ -1099,6 +1099,59 @@ int ft_psola_marks_warp(const float* f0, int64_t f0_stride_b, int64_t f0_stride_
 int ft_psola_time_map(const int32_t* path, const int32_t* path_len, int32_t* tmap, int B, int P, int TM, int hop, int w,
                       void* stream);
 
+/* ---- F0-adaptive spectral envelope and its mel-cepstrum (CheapTrick: Morise, "CheapTrick, a spectral envelope estimator for
+ * high-quality speech synthesis", Speech Communication 2015; the frequency transform of SPTK; csrc/envelope.hip; additive, the
+ * reference has no metric; a function added at ABI 15, no layout changes) ----------
+ * One launch, a workgroup per frame.  audio fp32 with ELEMENT strides (utterance, sample), read in place; n_samples [B] device
+ * int32, clamped inside the kernel to n = 1 ..= N; nothing at or behind n is read; utterance b gives the same bits alone as
+ * inside any batch.  f0 [B][T_f0] fp32 Hz with ELEMENT strides (utterance, frame), frame t centred on sample c = t hop,
+ * T_f0 >= T = N / hop + 1 (further frames are never read, nor is a frame above n / hop).  fft_size = 512, 1024 or 2048,
+ * H = fft_size / 2, df = sr / fft_size (exact: sr is an integer rate held in fp32).  sr15 = fp32(1.5 sr).
+ * This is CheapTrick as published with the two random-noise safeguards of the WORLD implementation replaced by one
+ * deterministic floor, and with step 5 summed directly (below).
+ *
+ * The integers.  Every integer the rule takes from F0 is formed from the fp32 f0 by these fp32 operations, each correctly rounded
+ * (no fast division, nothing contracted), so a float64 replay that forms them with fp32 takes the same window and the same bins:
+ *   f    = f0[t]  if  f0_floor <= f0[t] <= 1000  (NaN, infinities, 0 and negatives fail it),  else 500
+ *   half = min(int(floor(sr15 / f + 0.5)), H - 1)                 (the min never binds where fft_size follows from f0_floor)
+ *   wq   = f / df;          ul = min(2 + int(wq), H)
+ *   wb   = ((2 f) / 3) / df;     bnd = int(wb) + 1;     hw = 0.5 wb + 0.5;     n_w = min(int(hw), H);     fr = hw - float(n_w)
+ *   wd   = 2 hw - 1        (exact, as fr is: the smoothing width in bins, 2 f / (3 df) as hw holds it, within an fp32 ulp of wb)
+ * f, wq, wd and fr enter the real-valued steps as these fp32 values.  What follows is real arithmetic: the kernel's is fp32 (three
+ * sums of step 2 and the phases of steps 2 and 6 in float64), the replay's float64; neither order nor rounding is pinned.
+ *   2. window.  i = -half ..= half:  idx = min(max(c + i, 0), n - 1)  (edge replication against the utterance's OWN n);
+ *      w_i = 0.5 cos(pi i f / sr15) + 0.5;   s_i = (x[idx] w_i - w_i (sum_i x[idx] w_i / sum_i w_i)) / sqrt(sum_i w_i^2)
+ *   3. P[k] = |DFT_{fft_size}(s zero-padded)[k]|^2,  k = 0 ..= H.
+ *   4. DC correction.  For k < ul - 1:  pos = wq - k (exact in fp32), j = int(pos), g = pos - j;
+ *      P'[k] = P[k] + P[j] + g (P[j + 1] - P[j])  -- the interpolation reads the uncorrected P.  P'[k] = P[k] elsewhere.
+ *   5. smoothing over width = wd df.  With the mirror  M[j] = P'[-j] for j < 0,  P'[2 H - j] for j > H,  P'[j] otherwise
+ *      (WORLD mirrors bnd bins at both ends; n_w <= bnd), S[k] is the mean over [k - wd / 2, k + wd / 2] (in bins) of the
+ *      piecewise-constant function that holds M[j] on [j - 1/2, j + 1/2), summed DIRECTLY:
+ *        S[k] = (sum_{j = k - n_w + 1}^{k + n_w - 1} M[j]  (ascending)  + fr (M[k - n_w] + M[k + n_w])) / wd + 1e-20
+ *      (n_w = 0: S[k] = P'[k] + 1e-20).  The difference of two values of a cumulative sum, WORLD's form, is the same number in
+ *      exact arithmetic and cancels in fp32: a prefix sum the size of the frame's power has an ulp at -72 dB of it.
+ *   6. liftering.  c2[q] = (1 / fft_size) sum_k L[k] cos(2 pi k q / fft_size) over the even extension L of log S, q = 0 ..= H;
+ *      for q >= 1, x = f q / sr:  c2[q] *= sin(pi x) / (pi x) ((1 - 2 q1) + 2 q1 cos(2 pi x)).
+ *      env[k] = exp(sum_q c2[q] cos(2 pi k q / fft_size) over the even extension of c2),  the POWER envelope.
+ *   7. mel-cepstrum.  c^[0] = c2[0] / 2, c^[q] = c2[q], c^[H] = c2[H] / 2 (the one-sided cepstrum of the log AMPLITUDE);
+ *      mc[m] = sum_q A[m][q] c^[q], m = 0 ..= order: lane l = 0 .. 63 adds q = l, l + 64, .. ascending and the lanes meet in the
+ *      butterfly acc_l + acc_{l xor off}, off = 32 .. 1.  A = freqt [order + 1][H + 1] device fp32: the matrix of SPTK's frequency
+ *      transform for alpha, made on the host in float64 by running its recursion over i = H .. 0 on unit vectors
+ *      (g_0 = c_i + a d_0;  g_1 = (1 - a^2) d_0 + a d_1;  g_j = d_{j-1} + a (d_j - g_{j-1})) and rounded once.
+ * twiddle [3 fft_size / 4][2] device fp32: (cos, -sin)(2 pi j / fft_size), float64 rounded once.
+ * env [B][T][H + 1] and mc [B][T][order + 1] fp32 contiguous; either may be NULL (not computed, not written: without env the third
+ * transform is not run); rows t > n / hop are 0.
+ * FT_EINVAL before any device call: a NULL pointer (but one of env, mc; freqt without mc), B, N or hop < 1, B > 65535, a negative
+ * stride, T_f0 < N / hop + 1, sr, sr15 or q1 not finite or sr not positive, f0_floor outside 0 < f0_floor <= 1000, order outside
+ * 1 ..= FT_ENVELOPE_MAX_ORDER or >= H, a window at f0_floor longer than fft_size, 1000 / df + 2 > min(H, 250).
+ * FT_EUNSUPPORTED: another fft_size.
+ * Measured: profiles/envelope_prof.txt.  NOT pinned against pyworld or pysptk: neither was available. */
+#define FT_ENVELOPE_MAX_ORDER 32
+int ft_spectral_envelope(const float* audio, int64_t stride_b, int64_t stride_n, const int32_t* n_samples, const float* f0,
+                         int64_t f0_stride_b, int64_t f0_stride_t, const float* twiddle, const float* freqt, float* env, float* mc,
+                         int B, int N, int T_f0, int hop, int fft_size, int order, float sr, float sr15, float f0_floor, float q1,
+                         void* stream);
+
 /* ---- attention-CTC loss (flowtron.py:155-182, 245-274) ------------------------------
  * lp [B,T,L] = attn_logprob in natural time order.  Per sample: classes {blank (logit blank_logprob), 1..K_b} with
  * K_b = in_lens[b], frames t < out_lens[b]; log_softmax over the classes, CTC against the target 1..K_b (blank 0),

@@ -15,21 +15,12 @@ import torch
 
 import audio_processing
 from flowtron_amd import _lib as L
-from stft_ref64 import TINY32, griffin_lim64, hann64, istft64, rel_l2, start_angles, stft64, wss64
+from stft_ref64 import griffin_lim64, inverse_bound, istft64, rel_l2, start_angles, stft64
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "griffin_lim.pt")
 EPS32 = float(np.finfo(np.float32).eps)
-
-
-def ola(frames, hop):
-    """overlap-add [B, 1024, T] -> [B, 1024 + hop (T-1)]."""
-    B, n_fft, T = frames.shape
-    out = np.zeros((B, n_fft + hop * (T - 1)))
-    for t in range(T):
-        out[:, t * hop:t * hop + n_fft] += frames[:, :, t]
-    return out
 
 
 def random_spectrum(seed, B, T):
@@ -48,26 +39,6 @@ def spectral_convergence(y, M, hop=256, win_length=1024):
     return float(np.linalg.norm(np.abs(stft64(y, 1024, hop, win_length)) - M) / np.linalg.norm(M))
 
 
-def inverse_bound(M, hop, win_length):
-    """Per-sample bound on |fp32 inverse - float64 restatement|.  One output x[m] of a frame's fp32 irfft is built from the
-    spectrum through log2(1024) = 10 levels of butterflies (three radix-8 passes and the split step); every level rounds
-    each partial sum once, and no partial sum exceeds A_t = sum over the full Hermitian spectrum of |X_t[k]| / 1024 (the
-    largest value any sample of that frame can take).  So |error of x[m]| <= c eps log2(1024) A_t, where c = 4 covers the
-    complex twiddle products (|relative error| <= sqrt(5) eps) and the sincosf of X = M e^{i phase} (<= 2 ulp).  The window
-    product, the overlap-add of <= ceil(1024 / hop) terms and the division by wss add a few eps of |y|; together with a
-    factor 2 of margin:  bound[n] = 8 eps log2(1024) sum_t w A_t / wss[u]  +  8 eps |y[n]|.  It is a worst case: FFT
-    rounding errors add up like a random walk, so the observed error is far below it (reported by the test)."""
-    B, _, T = M.shape
-    M = np.asarray(M, np.float64)
-    A = (2 * M.sum(axis=1) - M[:, 0] - M[:, 512]) / 1024                  # [B, T]
-    w = hann64(win_length, 1024)
-    env = ola(np.abs(w)[None, :, None] * A[:, None, :], hop)
-    wss = wss64(T, 1024, hop, win_length)
-    nz = wss > TINY32
-    env[:, nz] /= wss[nz]
-    return 8 * EPS32 * 10 * env[:, 512:env.shape[1] - 512]
-
-
 def check_inverse(M, P, hop, win_length, what):
     st = audio_processing.STFT(1024, hop, win_length).cuda()
     y = st.inverse(torch.from_numpy(M).cuda(), torch.from_numpy(P).cuda())
@@ -75,7 +46,7 @@ def check_inverse(M, P, hop, win_length, what):
     assert y.shape == (B, 1, hop * (T - 1)), (what, y.shape)
     y = y[:, 0].cpu().double().numpy()
     y64 = istft64(M, P, 1024, hop, win_length)[0]
-    bound = inverse_bound(M, hop, win_length) + 8 * EPS32 * np.abs(y64)
+    bound = inverse_bound(M, 1024, hop, win_length) + 8 * EPS32 * np.abs(y64)
     ratio = np.abs(y - y64) / bound
     print("%s: max |gpu - f64| / bound = %.3g, rel L2 %.2e" % (what, ratio.max(), rel_l2(y, y64)))
     assert ratio.max() <= 1.0, (what, ratio.max(), np.unravel_index(ratio.argmax(), ratio.shape))

@@ -14,7 +14,7 @@ import torch
 import audio_processing
 from call_count import count_calls
 from flowtron_amd import _lib as L
-from stft_ref64 import TINY32, griffin_lim64, istft64, mel64, rel_l2, start_angles, stft64
+from stft_ref64 import TINY32, griffin_lim64, istft64, istft_bound, istft_ratio, mel64, rel_l2, start_angles, stft64
 
 pytestmark = pytest.mark.gpu
 
@@ -94,6 +94,11 @@ def test_inverse_matches_float64(n_fft, hop, win, B, N):
     print("inverse n_fft %d hop %d win %d T %d: rel L2 %.2e, %d samples with wss <= FLT_MIN" % (n_fft, hop, win, T, e, zero.sum()))
     assert e <= INV_BOUND
     assert np.all(got[:, zero] == 0)
+    # every sample by itself (stft_ref64.istft_bound), against the float64 inverse on the very float32 window the kernel read
+    w32 = st.fft_window.cpu().numpy()
+    ratio = istft_ratio(got, istft64(M, P, n_fft, hop, win, w32)[0], istft_bound(M, P, n_fft, hop, win, None, w32))
+    print("inverse n_fft %d hop %d win %d T %d: max |gpu - f64| / bound = %.3g" % (n_fft, hop, win, T, ratio.max()))
+    assert ratio.max() <= 1.0, (ratio.max(), np.unravel_index(ratio.argmax(), ratio.shape))
     y2 = st.inverse(torch.from_numpy(M).cuda(), torch.from_numpy(P).cuda())
     assert torch.equal(y, y2)
 

@@ -54,13 +54,18 @@ GEMM_GROUP_MAX = 48        # problems one ft_gemm_img_group call takes
 
 class LstmFwdRole(C.Structure):
     _fields_ = [("gx", _p), ("lens", _p), ("y", _p), ("ldy", _l), ("gates", _p), ("cell", _p), ("wimg", _p), ("state_h", _p), ("state_c", _p),
-                ("B", C.c_int32), ("ldb", C.c_int32), ("t0", C.c_int32), ("t1", C.c_int32), ("gx16", C.c_int32)]
+                ("B", C.c_int32), ("ldb", C.c_int32), ("t0", C.c_int32), ("t1", C.c_int32), ("gx16", C.c_int32),
+                ("x_img", _p), ("wih_img", _p), ("x_bias", _p), ("x_ld", _l), ("wih_ld", _l), ("x_rows", _l), ("xproj_k", C.c_int32)]
 
 
 class LstmBwdRole(C.Structure):
     _fields_ = [("dy", _p), ("ldy", _l), ("lens", _p), ("gates", _p), ("cell", _p), ("dgx", _p), ("wimg", _p),
                 ("dimg", _p), ("dimg_ld", _l), ("dimg_rows", _l), ("dbias", _p), ("state_da", _p), ("state_dc", _p),
                 ("B", C.c_int32), ("ldb", C.c_int32), ("t0", C.c_int32), ("t1", C.c_int32), ("carry_in", C.c_int32)]
+
+
+class WfragDesc(C.Structure):
+    _fields_ = [("w_hh", _p), ("fwd_img", _p), ("bwd_img", _p)]
 
 
 class ImgDesc(C.Structure):
@@ -152,6 +157,7 @@ SIGNATURES = {
     "ft_lstm_roles_debug_prof": ([_p], _i),
     "ft_lstm_roles_prepare_fwd": ([_p, _p, _i, _p], _i),
     "ft_lstm_roles_prepare_bwd": ([_p, _p, _i, _p], _i),
+    "ft_lstm_roles_prepare_table": ([C.POINTER(WfragDesc), _i, _i, _p], _i),
     "ft_lstm_roles_fwd": ([C.POINTER(LstmFwdRole), _i, _i, _i, _p, _i, _p, _i, _p], _i),
     "ft_lstm_roles_bwd": ([C.POINTER(LstmBwdRole), _i, _i, _i, _p, _i, _p, _i, _p], _i),
     "ft_lstm2_supported": ([_i, _i], _i),
@@ -255,7 +261,7 @@ MIXTURE_MAX_C = 64         # FT_MIXTURE_MAX_C
 
 # fp16-operand twins (include/flowtron_hip.h, end): same signatures, suffix _f16
 OP16_TWINS = ("ft_gemm", "ft_bf16_image", "ft_bf16_image_colsum", "ft_bf16_image_colsum_acc", "ft_bf16_image_rows_acc", "ft_bf16_image_rows_act_bwd_acc", "ft_gemm_img", "ft_gemm_img_group", "ft_bf16_image_rows", "ft_bf16_image_rows_into", "ft_bf16_image_rows_act_bwd", "ft_img_gemv_rows", "ft_img_gemv_rows_bwd", "ft_lstm_seq_fwd", "ft_lstm_seq_bwd",
-              "ft_lstm_persist_bwd", "ft_lstm_persist_bwd_img", "ft_lstm_roles_prepare_fwd", "ft_lstm_roles_prepare_bwd", "ft_lstm_roles_fwd", "ft_lstm_roles_bwd", "ft_lstm2_seq_fwd", "ft_lstm2_seq_bwd",
+              "ft_lstm_persist_bwd", "ft_lstm_persist_bwd_img", "ft_lstm_roles_prepare_fwd", "ft_lstm_roles_prepare_bwd", "ft_lstm_roles_prepare_table", "ft_lstm_roles_fwd", "ft_lstm_roles_bwd", "ft_lstm2_seq_fwd", "ft_lstm2_seq_bwd",
               "ft_lstm_bidir_seq_fwd", "ft_lstm_bidir_seq_bwd", "ft_bilstm_persist_fwd", "ft_bilstm_persist_bwd")
 for _n in OP16_TWINS:
     SIGNATURES[_n + "_f16"] = SIGNATURES[_n]

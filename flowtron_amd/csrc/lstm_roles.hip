@@ -41,6 +41,9 @@ struct FwdRoleP {
     const unsigned short* wfrag;         // make_wfrag_fwd_ug image
     float* st_h; float* st_c;            // [B][H]: read when t0 > 0, written at the end (either may be null together)
     int B, LB, t0, t1;
+    // XP kernels (the bursts compute their gx slice): compact row-mapped 16-bit image of x, k-contiguous 16-bit image of W_ih, fp32 bias
+    const unsigned short* ximg; const unsigned short* wih; const float* xbias;
+    long xld, wld; int xrows, K;
 };                                       // (gx: fp32 rows, or 16-bit rows of the build's operand format in the GX16 kernels)
 struct FwdLaunchP {
     FwdRoleP role[2];
@@ -50,6 +53,26 @@ struct FwdLaunchP {
     int phase, reset_rows;
     int* status; long timeout_ticks; long* prof;
 };
+
+// 16x16x32 MFMA with every operand in ARCHITECTURAL registers, as inline asm (the XP bursts of lstm_roles_fwd_k).  The builtin lets the
+// compiler pick the accumulator's register file, and with all 256 accumulation registers parked under W_hh it picked a[0:3]: W_hh's first
+// fragment then lived in VGPRs and was moved back (v_accvgpr_write) right in front of the asm MFMA of the step that reads it -- a VALU
+// write -> MFMA source read without wait states.  Two wait states in front for operands a VALU select has just written; the CALLER
+// keeps >= 3 other MFMAs between two accumulations into the same registers and 12 wait states before a VALU read (see mfma16_bagpr).
+__device__ __forceinline__ void mfma16_v_first(f32x4& acc, const bf16x8& a, const bf16x8& b) {                // acc = a x b (C = 0)
+#if FT_OPFMT == 1
+    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
+#else
+    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(acc) : "v"(a), "v"(b));
+#endif
+}
+__device__ __forceinline__ void mfma16_v(f32x4& acc, const bf16x8& a, const bf16x8& b) {
+#if FT_OPFMT == 1
+    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+#else
+    asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+#endif
+}
 
 template <typename T>
 __device__ __forceinline__ T* uniform_ptr(T* p) {                                  // a pointer the caller knows to be wave-uniform, in SGPRs
@@ -74,8 +97,15 @@ __device__ __forceinline__ void preset_other(uint4* other, size_t n16, unsigned*
 // GX16: the input-projection rows gx arrive as 16-BIT values of the operand format (written by the projection GEMM's epilogue,
 // FT_GEMM_C16) instead of fp32: half the bytes the GEMM writes and the bursts read, twice the steps per burst in the same LDS; the
 // value is widened exactly and added to the fp32 recurrent sums like the fp32 row was (round 6; VERDICT r5 #1c)
-template <int R, bool PROF, bool GX16>
+// XP (with GX16's LDS layout): there are NO gx rows in memory -- a burst COMPUTES its slice, the group's R rows x SB steps x this CU's 128
+// gate columns of x W_ih^T + bias, from the 16-bit operand images the projection GEMM would have read (both L2-resident and shared by
+// the group's 32 CUs; K <= 128: at most four 16x16x32 MFMAs per output tile), sums it like gemm_bf16_body at KS = 32 (one accumulator
+// per output, k ascending, each k on the same operand lane position, the weight fragment as the first operand), adds the bias and
+// rounds like the FT_GEMM_C16 epilogue: the 16-bit values the step reads are the ones the GEMM wrote.  Compact image row of
+// (t, b) = sum_{b' < b} (len_b' + 1) + t (rowmap_k); a lane's row index is clamped to its utterance's rows [.., len_b] and to the image.
+template <int R, bool PROF, bool GX16, bool XP = false>
 __global__ __launch_bounds__(256, 1) void lstm_roles_fwd_k(FwdLaunchP P) {
+    static_assert(!XP || (GX16 && R <= 8), "computed bursts: the 16-bit burst layout, 4 or 8 rows per group");
     // Epilogue layout.  R = 4 (the round-5 arrangement): waves 0-1 own one element each and run the cell update, waves 2-3 store the saved
     // tensors of the previous step out of LDS.  R >= 8 (SPLIT): ALL FOUR waves own R / 8 elements each (rows er0 + 8 e) and store their
     // own saved tensors straight from registers behind their publish -- two elements per thread on half the waves put 0.57 us of cell
@@ -143,11 +173,79 @@ __global__ __launch_bounds__(256, 1) void lstm_roles_fwd_k(FwdLaunchP P) {
     // ---- gx rows arrive in synchronous bursts of SB steps by 1 KiB LDS-DMA pieces: piece pi of a step = floats [256 pi, 256 pi + 256) of
     // its [gate][row][unit] block (R / 2 pieces per step)
     const int wu = __builtin_amdgcn_readfirstlane(wave);
+    // XP: MFMA column m = li of every (step, row) tile is batch row li % R of the group (16 % R == 0): one utterance per lane
+    int xbase = 0, xlen = 0;
+    bool xok = false;
+    if constexpr (XP) {
+        const int xb = b0 + (li & (R - 1));
+        xok = xb < B;
+        if (xok) {
+            for (int i = 0; i < xb; ++i) { const int l = p.lens[i]; xbase += (l < 0 ? 0 : l) + 1; }
+            xlen = p.lens[xb];
+            xlen = xlen < 0 ? 0 : xlen;
+        }
+    }
     auto burst = [&](int t) {
         __syncthreads();
         const int nst = (tg - t) < SB ? (tg - t) : SB;
         const unsigned dst0 = (unsigned)(size_t)(lds_void*)gxs;
-        if constexpr (GX16) {
+        if constexpr (XP) {
+            constexpr int SPT = 16 / R;                           // steps per 16-column tile; SB / SPT = 16 tiles, tile 4 i + wave is this wave's
+            const int K = p.K, nk = (K + 31) >> 5;
+            const bf16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+            bf16x8 xf[4][4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int st = (4 * i + wu) * SPT + (li / R);
+                int tt = t + st;
+                tt = tt < xlen ? tt : xlen;                       // (the separator row at the most: never another utterance's rows)
+                int ri = xbase + tt;
+                ri = ri < p.xrows ? ri : p.xrows - 1;
+                const unsigned short* xr = p.ximg + (size_t)ri * p.xld + kg * 8;
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks)
+                    xf[i][ks] = (xok && (4 * i + wu) * SPT < nst && ks * 32 + kg * 8 < K) ? *reinterpret_cast<const bf16x8*>(xr + ks * 32) : zero8;
+            }
+            // column tile jt = 16 consecutive units of one gate: gate jt >> 1, units 16 (jt & 1) ..; its weight fragments are fetched one
+            // tile ahead of the MFMAs that use them
+            auto wload = [&](int jt, bf16x8 (&wf)[4], f32x4& bias) {
+                const int col = (jt >> 1) * PH + q * UPC + (jt & 1) * 16;
+                const unsigned short* wr = p.wih + (size_t)(col + li) * p.wld + kg * 8;
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) wf[ks] = (ks * 32 + kg * 8 < K) ? *reinterpret_cast<const bf16x8*>(wr + ks * 32) : zero8;
+                bias = *reinterpret_cast<const f32x4*>(p.xbias + col + kg * 4);
+            };
+            bf16x8 wf[2][4];
+            f32x4 bs[2];
+            wload(0, wf[0], bs[0]);
+            unsigned short* const gxs16 = reinterpret_cast<unsigned short*>(gxs);
+#pragma unroll
+            for (int jt = 0; jt < 8; ++jt) {
+                if (jt + 1 < 8) wload(jt + 1, wf[(jt + 1) & 1], bs[(jt + 1) & 1]);
+                // the wave's four tiles side by side, k-step by k-step: three other MFMAs between two accumulations into the same registers
+                // (mfma16_v: asm MFMAs -- tiles beyond the burst's last step multiply zeros rather than shorten that distance)
+                f32x4 acc[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) mfma16_v_first(acc[i], wf[jt & 1][0], xf[i][0]);
+#pragma unroll
+                for (int ks = 1; ks < 4; ++ks) {
+                    if (ks >= nk) break;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) mfma16_v(acc[i], wf[jt & 1][ks], xf[i][ks]);
+                }
+                asm volatile("s_nop 7\n\ts_nop 3" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));     // 12 wait states before the results are read
+                const f32x4 b4 = bs[jt & 1];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    // lane (kg, li), register r: unit 16 (jt & 1) + 4 kg + r of gate jt >> 1, step and row of column li
+                    const int st = (4 * i + wu) * SPT + (li / R);
+                    uint2 pk;
+                    pk.x = pack_op16x2(acc[i][0] + b4[0], acc[i][1] + b4[1]);
+                    pk.y = pack_op16x2(acc[i][2] + b4[2], acc[i][3] + b4[3]);
+                    *reinterpret_cast<uint2*>(gxs16 + ((st * 4 + (jt >> 1)) * R + (li & (R - 1))) * UPC + (jt & 1) * 16 + kg * 4) = pk;
+                }
+            }
+        } else if constexpr (GX16) {
             // 16-bit rows: a step's [gate][row][unit] block is R / 4 pieces of 1 KiB (512 values, eight per lane)
             const unsigned short* gx16 = reinterpret_cast<const unsigned short*>(p.gx);
 #pragma unroll
@@ -892,10 +990,55 @@ __global__ __launch_bounds__(256, 1) void lstm_roles_bwd_k(BwdLaunchP P) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Descriptor table (ft_lstm_roles_prepare_table): the fragment images of up to WFRAG_TABLE_MAX recurrent weights in ONE launch -- a
+// training step makes six forward and six backward images in twelve launches of 5-12 us, each re-reading an fp32 weight.  A workgroup
+// owns (weight, CU slot q, column block cc): the 4 gates x 32 units x 128 columns of W_hh that hold everything of 32 forward tiles
+// (jb = 8 q .., chunks 4 cc ..) and of 32 backward tiles (jt = 8 cc .., the four gate chunks) -- read ONCE, rounded into LDS, written as
+// whole 1 KiB fragments of both images.  The values are make_wfrag_fwd_ug's and make_wfrag_rs's: f2op16 of the same elements.
+constexpr int WFRAG_TABLE_MAX = 16;
+struct WfragTable {
+    const float* w[WFRAG_TABLE_MAX]; unsigned short* fwd[WFRAG_TABLE_MAX]; unsigned short* bwd[WFRAG_TABLE_MAX];
+};
+__global__ __launch_bounds__(256) void make_wfrag_table_k(WfragTable tab) {
+    constexpr int TS = 128 + 8;                                    // tile row stride (16-bit values): 272 bytes, 16-byte aligned rows
+    __shared__ __attribute__((aligned(16))) unsigned short tile[128 * TS];      // row = gate * 32 + unit, 128 columns
+    const int tid = threadIdx.x, wi = blockIdx.x >> 8, q = (blockIdx.x >> 3) & 31, cc = blockIdx.x & 7;
+    const float* __restrict__ w = tab.w[wi];
+    unsigned short* const fwd = tab.fwd[wi];
+    unsigned short* const bwd = tab.bwd[wi];
+#pragma unroll 4
+    for (int pass = 0; pass < 16; ++pass) {
+        const int row = pass * 8 + (tid >> 5), c4 = (tid & 31) * 4;
+        const float4 v = *reinterpret_cast<const float4*>(w + ((size_t)(row >> 5) * PH + q * 32 + (row & 31)) * PH + cc * 128 + c4);
+        *reinterpret_cast<uint2*>(&tile[row * TS + c4]) = make_uint2((unsigned)f2op16(v.x) | ((unsigned)f2op16(v.y) << 16),
+                                                                     (unsigned)f2op16(v.z) | ((unsigned)f2op16(v.w) << 16));
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int it = 0; it < 8; ++it) {
+        const int p = it * 256 + tid, lane = p & 63, a = (p >> 6) & 3, b = p >> 8;
+        const int li = lane & 15, kg = lane >> 4;
+        if (fwd) {
+            // tile jb = 8 q + b, chunk 4 cc + a, lane (kg, li), e  <-  W_hh[(li & 3) H + 4 jb + (li >> 2)][32 c + 8 kg + e]
+            const uint4 v = *reinterpret_cast<const uint4*>(&tile[((li & 3) * 32 + b * 4 + (li >> 2)) * TS + a * 32 + kg * 8]);
+            *reinterpret_cast<uint4*>(fwd + ((size_t)((q * 8 + b) * NCHUNK + cc * 4 + a) * 64 + lane) * 8) = v;
+        }
+        if (bwd) {
+            // CU slot q, tile jt = 8 cc + b, chunk (= gate) a, lane (kg, li), e  <-  W_hh[a H + 32 q + 8 kg + e][16 jt + li]
+            unsigned s[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s[e] = tile[(a * 32 + kg * 8 + e) * TS + b * 16 + li];
+            *reinterpret_cast<uint4*>(bwd + ((size_t)((q * (PH / 16) + cc * 8 + b) * 4 + a) * 64 + lane) * 8) =
+                make_uint4(s[0] | (s[1] << 16), s[2] | (s[3] << 16), s[4] | (s[5] << 16), s[6] | (s[7] << 16));
+        }
+    }
+}
+
 }  // namespace
 
 #if FT_OPFMT == 0
-long* ftint_roles_prof = nullptr;                    // shared with the fp16 build of this file
+long* ftint_roles_prof = nullptr;                   // shared with the fp16 build of this file
 extern "C" int ft_lstm_roles_debug_prof(void* dev_buf) { ftint_roles_prof = reinterpret_cast<long*>(dev_buf); return FT_OK; }
 extern "C" size_t ft_lstm_roles_ctx_bytes(void) { return CTX_BYTES; }
 extern "C" size_t ft_lstm_roles_wimg_bytes(int H) { return (size_t)4 * H * H * 2; }
@@ -927,6 +1070,20 @@ extern "C" int FT_OPNAME(ft_lstm_roles_prepare_bwd)(const float* w_hh, void* wim
     return FT_OK;
 }
 
+extern "C" int FT_OPNAME(ft_lstm_roles_prepare_table)(const ft_wfrag_desc* descs, int n, int H, void* stream) {
+    FT_CHECK_ARG(descs && n >= 1 && n <= WFRAG_TABLE_MAX && H == PH);
+    WfragTable t{};
+    for (int i = 0; i < n; ++i) {
+        const ft_wfrag_desc& d = descs[i];
+        FT_CHECK_ARG(d.w_hh && (d.fwd_img || d.bwd_img) && reinterpret_cast<uintptr_t>(d.w_hh) % 16 == 0 &&
+                     reinterpret_cast<uintptr_t>(d.fwd_img) % 256 == 0 && reinterpret_cast<uintptr_t>(d.bwd_img) % 256 == 0);
+        t.w[i] = d.w_hh; t.fwd[i] = reinterpret_cast<unsigned short*>(d.fwd_img); t.bwd[i] = reinterpret_cast<unsigned short*>(d.bwd_img);
+    }
+    hipLaunchKernelGGL(make_wfrag_table_k, dim3(n * 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), t);
+    FT_CHECK_LAUNCH();
+    return FT_OK;
+}
+
 template <typename K, typename PT>
 static int roles_launch(K kern, size_t lds, const PT& P, hipStream_t st) {
     FT_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -942,16 +1099,28 @@ extern "C" int FT_OPNAME(ft_lstm_roles_fwd)(const ft_lstm_fwd_role* roles, int n
     if (H != PH || !ft_lstm_persist_supported(8, H))
         return ft_fail(FT_EUNSUPPORTED, "ft_lstm_roles_fwd: needs H == 1024 and a 256-CU device (H=%d)", H);
     FwdLaunchP P{};
-    bool any = false, g16 = false;
+    bool any = false, g16 = false, xp = false;
     for (int i = 0; i < n_roles; ++i) {
         const ft_lstm_fwd_role& r = roles[i];
-        FT_CHECK_ARG(r.gx && r.lens && r.y && r.wimg && r.B >= 1 && r.B <= (8 / n_roles) * R && r.ldb >= r.B && r.ldy >= H);
+        FT_CHECK_ARG((r.xproj_k != 0 || r.gx) && r.lens && r.y && r.wimg && r.B >= 1 && r.B <= (8 / n_roles) * R && r.ldb >= r.B && r.ldy >= H);
         FT_CHECK_ARG((r.gates == nullptr) == (r.cell == nullptr) && (r.state_h == nullptr) == (r.state_c == nullptr));
         FT_CHECK_ARG(r.t0 >= 0 && r.t1 >= r.t0 && (r.t0 == 0 || r.state_h) && reinterpret_cast<uintptr_t>(r.gx) % 16 == 0);
         P.role[i] = FwdRoleP{reinterpret_cast<const float*>(r.gx), r.lens, r.y, (long)r.ldy, r.gates, r.cell, reinterpret_cast<const unsigned short*>(r.wimg),
                              r.state_h, r.state_c, r.B, r.ldb, r.t0, r.t1};
-        FT_CHECK_ARG(i == 0 || (r.gx16 != 0) == g16);             // one gx format per launch (the kernel is instantiated on it)
+        if (r.xproj_k != 0) {
+            // the bursts compute gx: 16-byte fragments from both images (k-contiguous, rows 16-byte aligned), whole 8-value pieces only
+            FT_CHECK_ARG(R <= 8 && r.xproj_k >= 8 && r.xproj_k <= 128 && r.xproj_k % 8 == 0 && r.x_img && r.wih_img && r.x_bias);
+            FT_CHECK_ARG(reinterpret_cast<uintptr_t>(r.x_img) % 16 == 0 && reinterpret_cast<uintptr_t>(r.wih_img) % 16 == 0 &&
+                         reinterpret_cast<uintptr_t>(r.x_bias) % 16 == 0);
+            FT_CHECK_ARG(r.x_ld >= r.xproj_k && r.x_ld % 8 == 0 && r.wih_ld >= r.xproj_k && r.wih_ld % 8 == 0 && r.x_rows >= 1 && r.x_rows < (1ll << 31));
+            FwdRoleP& fp = P.role[i];
+            fp.ximg = reinterpret_cast<const unsigned short*>(r.x_img); fp.wih = reinterpret_cast<const unsigned short*>(r.wih_img);
+            fp.xbias = r.x_bias; fp.xld = (long)r.x_ld; fp.wld = (long)r.wih_ld; fp.xrows = (int)r.x_rows; fp.K = r.xproj_k;
+        }
+        // one projection mode per launch (the kernel is instantiated on it): fp32 gx rows, 16-bit gx rows, or computed bursts
+        FT_CHECK_ARG(i == 0 || ((r.gx16 != 0) == g16 && (r.xproj_k != 0) == xp));
         g16 = r.gx16 != 0;
+        xp = r.xproj_k != 0;
         any = any || r.t1 > r.t0;
     }
     // a launch with every window empty would do nothing, yet its caller counts it in `phase`: the next real launch would then work in
@@ -970,7 +1139,9 @@ extern "C" int FT_OPNAME(ft_lstm_roles_fwd)(const ft_lstm_fwd_role* roles, int n
 #define FT_ROLES_FWD(R_, SB_) \
     (g16 ? (pf ? roles_launch(lstm_roles_fwd_k<R_, true, true>, lds(R_, SB_), P, st) : roles_launch(lstm_roles_fwd_k<R_, false, true>, lds(R_, SB_), P, st)) \
          : (pf ? roles_launch(lstm_roles_fwd_k<R_, true, false>, lds(R_, SB_), P, st) : roles_launch(lstm_roles_fwd_k<R_, false, false>, lds(R_, SB_), P, st)))
-    if (R == 4) rc = FT_ROLES_FWD(4, 32);
+    if (xp && R == 4) rc = pf ? roles_launch(lstm_roles_fwd_k<4, true, true, true>, lds(4, 32), P, st) : roles_launch(lstm_roles_fwd_k<4, false, true, true>, lds(4, 32), P, st);
+    else if (xp) rc = pf ? roles_launch(lstm_roles_fwd_k<8, true, true, true>, lds(8, 16), P, st) : roles_launch(lstm_roles_fwd_k<8, false, true, true>, lds(8, 16), P, st);
+    else if (R == 4) rc = FT_ROLES_FWD(4, 32);
     else if (R == 8) rc = FT_ROLES_FWD(8, 16);
     else rc = FT_ROLES_FWD(16, 4);
 #undef FT_ROLES_FWD

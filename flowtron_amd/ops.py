@@ -236,7 +236,9 @@ class Bf16Image:
 
 # weight images of one forward pass in one launch (Bf16Image.of_weight): the plan = what the previous forward of the same model asked for
 _WIMG_ON = True
-_WIMG = {"plan": {}, "plan_next": None, "cache": {}, "armed": False, "plans": None}
+_WIMG = {"plan": {}, "plan_next": None, "cache": {}, "armed": False, "plans": None,
+         # the same for the recurrences' W_hh fragment images (roles_wimg): key -> [weight, its backward image is wanted too]
+         "wf_plan": {}, "wf_plan_next": None, "wf_cache": {}, "wf_armed": False, "wf_plans": None, "wf_last": None, "wf_grad": False}
 
 
 def weight_images_begin(model):
@@ -245,9 +247,12 @@ def weight_images_begin(model):
         return
     w = _WIMG
     if w["plans"] is None:
-        w["plans"] = _weakref.WeakKeyDictionary()
+        w["plans"], w["wf_plans"] = _weakref.WeakKeyDictionary(), _weakref.WeakKeyDictionary()
     w["plan"] = w["plans"].get(model, {})
     w["plan_next"], w["cache"], w["armed"] = {}, {}, bool(w["plan"])
+    w["wf_plan"] = w["wf_plans"].get(model, {})
+    w["wf_plan_next"], w["wf_cache"], w["wf_armed"], w["wf_last"] = {}, {}, bool(w["wf_plan"]), None
+    w["wf_grad"] = torch.is_grad_enabled()       # (read HERE: the requests come from inside autograd Functions, where it is off)
 
 
 def weight_images_end(model):
@@ -255,6 +260,11 @@ def weight_images_end(model):
     if w["plan_next"] is not None and w["plans"] is not None:
         w["plans"][model] = w["plan_next"]
     w["plan"], w["plan_next"], w["cache"], w["armed"] = {}, None, {}, False
+    if w["wf_plan_next"] is not None and w["wf_plans"] is not None:
+        w["wf_plans"][model] = w["wf_last"] = w["wf_plan_next"]      # (the pass's backward marks the entries whose backward image it asks for)
+    # forward images not taken are dropped here; backward images wait for this pass's backward
+    w["wf_cache"] = {k: v for k, v in w["wf_cache"].items() if k[1]}
+    w["wf_plan"], w["wf_plan_next"], w["wf_armed"] = {}, None, False
 
 
 # images of activations are shared between every consumer of the SAME tensor (h_att feeds the query projection, the gate and
@@ -1427,8 +1437,54 @@ def roles_ctx(device):
     return c
 
 
+WFRAG_TABLE_MAX = 16
+
+
+def _wfrag_planned(w_hh, mode, backward):
+    """roles_wimg inside the weight-image plan of a model (weight_images_begin): the image of a planned weight, made with all the others
+    in ONE launch at the forward's first request (ft_lstm_roles_prepare_table), or None.  A forward request of a parameter enters the
+    plan of the NEXT forward; a backward request marks its entry, so that the next forward with gradients enabled also makes the backward
+    image (gradient mode as weight_images_begin found it; it waits in the cache until the backward takes it, or until the next forward begins; taken only while the weight's version
+    is the one it was made from).  Every forward builds from the current values: nothing is kept from step to step."""
+    w = _WIMG
+    key = (w_hh.data_ptr(), tuple(w_hh.shape), mode)
+    if backward:
+        e = w["wf_last"].get(key) if w["wf_last"] is not None else None
+        if e is not None:
+            e[1] = True
+    elif w["wf_plan_next"] is not None and isinstance(w_hh, torch.nn.Parameter) and w_hh.shape[1] == PERSIST_H:
+        prev = w["wf_plan"].get(key)
+        w["wf_plan_next"][key] = [w_hh, bool(prev is not None and prev[1])]
+    if w["wf_armed"] and not backward:
+        w["wf_armed"] = False
+        nbytes = L.lib().ft_lstm_roles_wimg_bytes(PERSIST_H)
+        plan = [(k, t, bw) for k, (t, bw) in w["wf_plan"].items() if t.is_cuda and t.device == w_hh.device and t.dtype == torch.float32
+                and t.is_contiguous() and t.data_ptr() == k[0] and tuple(t.shape) == k[1]]
+        for fmt in sorted({k[2] for k, _, _ in plan}):
+            items = [p for p in plan if p[0][2] == fmt]
+            for lo in range(0, len(items), WFRAG_TABLE_MAX):
+                part = items[lo:lo + WFRAG_TABLE_MAX]
+                descs = (L.WfragDesc * len(part))()
+                for i, (k, t, bw) in enumerate(part):
+                    f_img = torch.empty(nbytes, device=t.device, dtype=torch.uint8)
+                    b_img = torch.empty(nbytes, device=t.device, dtype=torch.uint8) if bw and w["wf_grad"] else None
+                    descs[i] = L.WfragDesc(t.data_ptr(), L.ptr(f_img), L.ptr(b_img))
+                    w["wf_cache"][(k, False)] = (f_img, t, t._version)
+                    if b_img is not None:
+                        w["wf_cache"][(k, True)] = (b_img, t, t._version)
+                L.check(L.op16("ft_lstm_roles_prepare_table", fmt)(descs, len(part), PERSIST_H, L.stream()), "ft_lstm_roles_prepare_table")
+    hit = w["wf_cache"].pop((key, bool(backward)), None)
+    if hit is not None and hit[2] == w_hh._version:          # (same storage by the key; unchanged since the table read it)
+        return hit[0]
+    return None
+
+
 def roles_wimg(w_hh, mode, backward):
     """MFMA fragment image of W_hh for the roles kernels (forward: gate-adjacent tiles; backward: the reduce-scatter layout)."""
+    if _WIMG_ON:
+        img = _wfrag_planned(w_hh, mode, backward)
+        if img is not None:
+            return img
     img = torch.empty(L.lib().ft_lstm_roles_wimg_bytes(w_hh.shape[1]), device=w_hh.device, dtype=torch.uint8)
     fn = L.op16("ft_lstm_roles_prepare_bwd" if backward else "ft_lstm_roles_prepare_fwd", mode)
     w = _c(w_hh)                 # (named: a temporary copy would be recycled by the allocator before the launch reads it)
@@ -1436,8 +1492,19 @@ def roles_wimg(w_hh, mode, backward):
     return img
 
 
-def fwd_role(gx, lens, y, gates, cell, wimg, t0=0, t1=None, state=None, b0=0, nb=None):
-    """one forward recurrence of a roles launch over the batch rows [b0, b0 + nb) of time-major tensors, window [t0, t1)"""
+def fwd_role(gx, lens, y, gates, cell, wimg, t0=0, t1=None, state=None, b0=0, nb=None, xproj=None):
+    """one forward recurrence of a roles launch over the batch rows [b0, b0 + nb) of time-major tensors, window [t0, t1).
+    xproj = (x image over the RowMap of `lens`, W_ih image, fp32 bias [4H]): gx is None and the kernel's bursts compute their gx slices
+    from the images (the whole batch of the map: b0 == 0; R <= 8)"""
+    if xproj is not None:
+        x_img, w_img, bias = xproj
+        assert gx is None and b0 == 0 and x_img.fmt == w_img.fmt and x_img.cols == w_img.cols and bias.dtype == torch.float32
+        T, LB = y.shape[0], y.shape[1]
+        nb = LB if nb is None else nb
+        return L.LstmFwdRole(None, lens.data_ptr(), y.data_ptr(), y.stride(1), L.ptr(gates), L.ptr(cell), L.ptr(wimg),
+                             L.ptr(state[0]) if state is not None else None, L.ptr(state[1]) if state is not None else None,
+                             nb, LB, t0, T if t1 is None else t1, 0,
+                             x_img.ptr(), w_img.ptr(), L.ptr(bias), x_img.ld, w_img.ld, x_img.rows, x_img.cols)
     T, LB, H = gx.shape[0], gx.shape[1], y.shape[2]
     nb = LB - b0 if nb is None else nb
     return L.LstmFwdRole(gx.data_ptr() + gx.element_size() * 4 * H * b0, lens.data_ptr() + 4 * b0, y.data_ptr() + 4 * y.stride(1) * b0, y.stride(1),
@@ -1894,6 +1961,70 @@ class LSTMSeqFn(torch.autograd.Function):
         return _leave_dgates(dgx, d_img, (T, B, 4 * H), ctx.gx_dtype), dW, None, None, None, None, None
 
 
+_XPROJ = True     # a narrow input projection (K <= 128) inside the persistent forward recurrence's bursts; tests set it False for the two-kernel path
+XPROJ_MAX_K = 128
+
+
+def xproj_ok(mode, rowmap, T, B, H, reverse, xs, N, gate, device):
+    """whether lstm_layer runs projection + recurrence as ONE node whose forward kernel computes gx in its bursts (LSTMProjSeqFn):
+    everything gx16_ok asks of the two-kernel path (so the values are the ones that path's 16-bit rows hold), one narrow input, no
+    gate layer riding on the projection, and a roles plan of one launch at R <= 8"""
+    if not (_XPROJ and gate is None and len(xs) == 1 and xs[0].shape[-1] <= XPROJ_MAX_K and xs[0].shape[-1] % 8 == 0):
+        return False
+    if not gx16_ok(mode, rowmap, T, B, H, reverse, xs, N, device):
+        return False
+    plan = roles_plan(B, False)
+    return len(plan) == 1 and plan[0][2] <= 8
+
+
+class _NodeCtx:
+    """what a Function's static backward reads of its ctx, for a node that runs the backward of another node as a part of its own"""
+
+    def __init__(self, saved_tensors, needs_input_grad, **attrs):
+        self.saved_tensors, self.needs_input_grad = saved_tensors, needs_input_grad
+        self.__dict__.update(attrs)
+
+
+class LSTMProjSeqFn(torch.autograd.Function):
+    """y of an LSTM layer from x [T,B,K], K <= 128 (xproj_ok): LinearFn's 16-bit-row projection and LSTMSeqFn's persistent recurrence as one
+    node.  The forward makes the operand images LinearFn would make and hands them to the recurrence, whose bursts compute gx (csrc/
+    lstm_roles.hip, the XP kernels): no projection GEMM, no [T,B,4H] gx.  y / gates / cell are bit-identical to the two nodes'.  The backward
+    IS the two nodes' backward, run one after the other: the same kernels in the same order."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, bias, w_hh, lens, mode, rowmap, fill):
+        x, w_ih, bias, w_hh = _c(x), _c(w_ih), _c(bias), _c(w_hh)
+        L.require_cuda(x, w_ih, bias, w_hh, lens)
+        if bias.data_ptr() % 16:
+            bias = bias.clone()                   # (the kernel reads four bias values per lane)
+        T, B, K = x.shape
+        H = w_hh.shape[1]
+        w_img = Bf16Image.of_weight(w_ih, mode)
+        x_img = shared_image(x, T * B, K, mode, rowmap)
+        y, gates, cell = (torch.empty(T, B, n, device=x.device, dtype=torch.float32) for n in (H, 4 * H, H))
+        wimg = roles_wimg(w_hh, mode, False)
+        (_, _, R), = roles_plan(B, False)
+        roles_launch([fwd_role(None, lens, y, gates, cell, wimg, xproj=(x_img, w_img, bias))], R, mode, x.device)
+        ctx.imgs = (w_img, [x_img])
+        ctx.save_for_backward(x, w_ih, w_hh, lens, y, gates, cell)
+        ctx.mode, ctx.rowmap, ctx.fill = mode, rowmap, fill
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w_ih, w_hh, lens, y, gates, cell = ctx.saved_tensors
+        need = ctx.needs_input_grad               # x, w_ih, bias, w_hh
+        rec = _NodeCtx((w_hh, lens, y, gates, cell), (False, need[3]), reverse=False, mode=ctx.mode, rowmap=ctx.rowmap, gx_private=True,
+                       gx_dtype=op16_dtype(ctx.mode))
+        dgx, dW_hh = LSTMSeqFn.backward(rec, dy)[:2]
+        lin = _NodeCtx((w_ih, None, x), (need[1], need[2], False, False, False, False, need[0]), imgs=ctx.imgs, img_kind="images",
+                       lazy_img_mode=None, lazy_src=None, has_bias=True, act=L.ACT_NONE, rowmap=ctx.rowmap, fill=ctx.fill, cat=False,
+                       mode=ctx.mode, mode_dx=ctx.mode, mode_dw=ctx.mode)
+        g = LinearFn.backward(lin, dgx)
+        ctx.imgs = None                           # (a second backward through the graph makes them again: _linear_images_again)
+        return g[6], g[0], g[1], dW_hh, None, None, None, None
+
+
 MAX_STEP_BATCH = 64          # batch rows the launch-per-step recurrences and the bidirectional pair chain take (csrc/lstm.hip)
 
 
@@ -1922,6 +2053,8 @@ def lstm_layer(x, lens, w_ih, w_hh, b_ih, b_hh, reverse=False, mode=None, xs_ext
         w_ih_p, w_hh_p, b_p = pad_gate_blocks(w_ih, 0), pad_gate_blocks(w_hh, PERSIST_H - H), pad_gate_blocks(bias_sum(b_ih, b_hh), 0)
         out = lstm_layer(x, lens, w_ih_p, w_hh_p, b_p, torch.zeros_like(b_p), reverse, mode, xs_extra, rowmap, fill, gate)
         return out[..., :H].contiguous() if gate is None else (out[0][..., :H].contiguous(), out[1])
+    if xproj_ok(mode, rowmap, T, B, H, reverse, xs, w_ih.shape[0], gate, x.device):
+        return LSTMProjSeqFn.apply(x, w_ih, bias_sum(b_ih, b_hh), w_hh, lens, mode, rowmap, fill)
     gx, gates, private = _input_projection(xs, w_ih, bias_sum(b_ih, b_hh), H, reverse, mode, rowmap, fill, gate)
     if B > MAX_STEP_BATCH and not lstm_persistent(B, H, reverse, mode, gx.device):
         # the launch-per-step kernels take at most 64 batch rows (the reference's nn.LSTM takes any, flowtron.py:654-655): the rows

@@ -355,6 +355,17 @@ typedef struct {
     int32_t B, ldb, t0, t1;
     int32_t gx16;                        /* 0: gx = fp32 rows [T][ldb][4H]; 1: 16-bit rows of the call's operand format (what ft_gemm_img writes with
                                           * FT_GEMM_C16: half the bytes; widened exactly before it is added to the fp32 recurrent sums) -- one format per launch */
+    /* Trailing fields (appended without a new ABI number, like ft_gemm_img_args.a_rows: callers zero-initialise the struct).  xproj_k != 0:
+     * there is NO gx (gx may be NULL, gx16 is ignored) -- the kernel computes gx = x W_ih^T + bias itself, slice by slice, from the 16-bit
+     * operand images the projection GEMM would read, with that GEMM's summation and FT_GEMM_C16's rounding: y / gates / cell are
+     * bit-identical to ft_gemm_img(FT_GEMM_C16) + gx16.  x_img: the compact row-mapped image of x (ft_bf16_image_rows over ft_rowmap_build
+     * of `lens`: row of (t, b) = sum_{b' < b} (lens[b'] + 1) + t; x_rows rows of x_ld elements); the role must start at batch row 0 of that
+     * map.  wih_img: the k-contiguous image of W_ih [4H][K] (ft_bf16_image; wih_ld elements per row).  x_bias: fp32 [4H] (b_ih + b_hh).
+     * xproj_k = K: a multiple of 8, <= 128.  Images and bias 16-byte aligned, strides multiples of 8.  rows_per_group 4 or 8 only; one
+     * projection mode per launch. */
+    const void* x_img; const void* wih_img; const float* x_bias;
+    int64_t x_ld, wih_ld, x_rows;
+    int32_t xproj_k;
 } ft_lstm_fwd_role;
 typedef struct {
     const float* dy; int64_t ldy; const int32_t* lens; const float* gates; const float* cell;
@@ -371,6 +382,12 @@ int ft_lstm_roles_ctx_init(void* ctx, void* stream);
 int ft_lstm_roles_debug_prof(void* dev_buf);        /* as ft_lstm_persist_debug_prof, for the kernels below */
 int ft_lstm_roles_prepare_fwd(const float* w_hh, void* wimg, int H, void* stream);
 int ft_lstm_roles_prepare_bwd(const float* w_hh, void* wimg, int H, void* stream);
+/* The fragment images of up to 16 recurrent weights in ONE launch: each fp32 W_hh [4H][H] (contiguous, 16-byte aligned) is read once
+ * and written as its forward image (fwd_img, what ft_lstm_roles_prepare_fwd makes) and / or its backward image (bwd_img, what
+ * ft_lstm_roles_prepare_bwd makes -- also the image ft_lstm_persist_bwd builds for itself); a NULL destination is skipped, at least one
+ * per weight is set.  Byte-identical to the per-weight entries. */
+typedef struct { const float* w_hh; void* fwd_img; void* bwd_img; } ft_wfrag_desc;
+int ft_lstm_roles_prepare_table(const ft_wfrag_desc* descs, int n, int H, void* stream);
 int ft_lstm_roles_fwd(const ft_lstm_fwd_role* roles, int n_roles, int rows_per_group, int reset_rows, void* ctx, int phase,
                       int32_t* status, int H, void* stream);
 int ft_lstm_roles_bwd(const ft_lstm_bwd_role* roles, int n_roles, int rows_per_group, int reset_rows, void* ctx, int phase,
@@ -1311,6 +1328,7 @@ int ft_lstm_persist_bwd_img_f16(const float* dy, int64_t ldy, const float* w_hh,
                             void* dimg, int64_t dimg_ld, int64_t dimg_rows, float* dbias, void* stream);
 int ft_lstm_roles_prepare_fwd_f16(const float* w_hh, void* wimg, int H, void* stream);
 int ft_lstm_roles_prepare_bwd_f16(const float* w_hh, void* wimg, int H, void* stream);
+int ft_lstm_roles_prepare_table_f16(const ft_wfrag_desc* descs, int n, int H, void* stream);
 int ft_lstm_roles_fwd_f16(const ft_lstm_fwd_role* roles, int n_roles, int rows_per_group, int reset_rows, void* ctx, int phase,
                           int32_t* status, int H, void* stream);
 int ft_lstm_roles_bwd_f16(const ft_lstm_bwd_role* roles, int n_roles, int rows_per_group, int reset_rows, void* ctx, int phase,
